@@ -1,15 +1,25 @@
 """Benchmark of the PnP-Flow restoration hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload c2_256|c2|c3|c4|c5|tiny]
+    python bench.py --gpus N --steps K --warmup W [--workload c2_256|c2|c3|c4|c5|tiny] [--dump-outputs DIR] [--full]
 
 A "step" = one full PnP-Flow restoration (steps_pnp=100 outer iterations x num_samples=5
 U-Net evaluations + data-fidelity / interpolation / averaging kernels) of ONE batch of
 synthetic degraded images that already resides in HBM.  Default workload = the configuration
 BASELINE.json's `metric` is quoted on: CelebA-shaped 256x256 box inpainting (half-size 40,
 sigma 0.05, alpha 0.5 - the reference's main.py:132-136 at 256^2), pnp_flow, batch 32 per GPU,
-100 x 5; BASELINE configs[1] (the 128x128 case) and the other configs are timed beside it in
-`configs`.  Each rank restores its own batch (independent units, weak scaling); the only
-collective is the final all_gather of per-image PSNR.  Rank 0 prints ONE JSON line.
+100 x 5.  Each rank restores its own batch (independent units, weak scaling).  Rank 0 prints
+ONE JSON line.
+
+A plain run sets up, runs W warm-up steps, times K steps and prints the headline (`value`,
+`ms_per_step`).  `--full` adds everything else the line can carry, each with runs of its own:
+per-image PSNR (all_gathered in global image order), board power over the timed steps, the conv
+roofline with the box's streaming / MFMA ceilings, the CPU baseline, BASELINE configs[1..4]
+beside the headline in `configs`, precision mode 2, the NCSN++ forward and the pointwise block.
+
+`--dump-outputs DIR` writes what the last timed step returned - the restored images of the global
+batch, in global image order - as DIR/restored.npy (float32; a fixed, seeded sample of whole
+images when the batch exceeds 64 MB).  The inputs depend only on the arguments, so two builds
+can be compared output for output.
 
 `--gpus N` IS the job size: with N > 1 and no torchrun environment the script re-executes itself
 under `python -m torch.distributed.run --nproc-per-node N` (one process per GPU, backend "nccl" =
@@ -611,6 +621,21 @@ def resolve_job(gpus):
     return int(os.environ.get("RANK", "0")), world
 
 
+DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs writes at most this much
+
+
+def dump_outputs(path, x, seed=0):
+    """DIR/restored.npy: the restored images `x` (global batch, global image order) as float32.  Above DUMP_BYTES, a fixed
+    sample of whole images (numpy Philox keyed by `seed`, kept in image order) that fits."""
+    arr = x.detach().float().cpu().numpy()
+    if arr.nbytes > DUMP_BYTES - 4096:       # room for the .npy header
+        k = max(1, (DUMP_BYTES - 4096) // arr[0].nbytes)
+        idx = np.sort(np.random.Generator(np.random.Philox(key=[seed, 0])).choice(len(arr), size=k, replace=False))
+        arr = arr[idx]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "restored.npy"), np.ascontiguousarray(arr, dtype=np.float32))
+
+
 def dry_run(a, rank, world, backend):
     """PNPFLOW_BENCH_DRY=1: the launch / rendezvous / reduction path of the bench without any GPU work (CPU containers: the
     `--gpus N` contract is testable where there is no device).  Prints the same line shape with "dry_run": true."""
@@ -639,18 +664,26 @@ def main():
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="c2_256", choices=list(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary BASELINE configs and the pointwise block (N=1 default runs include them)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: PSNR, board power, conv roofline, CPU baseline, the other "
+                         "BASELINE configs, precision mode 2, NCSN++ forward, pointwise block (each narrowed by the --no-* options)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the restored images of the last timed step to DIR/restored.npy (float32, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary BASELINE configs, the pointwise block and the live traffic passes")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--batch", type=int, default=0, help="override the workload's batch per GPU (tests)")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed (backend 'nccl' = RCCL) even for a one-rank job and execute the job's collectives "
-                         "(barrier, all_reduce(MAX) of the step time, all_gather of the per-image PSNR) on device tensors: the RCCL path on a 1-GPU box")
+                         "(barrier, all_reduce(MAX) of the step time; with --full the all_gather of the per-image PSNR) on device tensors: the RCCL "
+                         "path on a 1-GPU box")
     ap.add_argument("--precision", type=int, default=1, choices=[0, 1, 2],
                     help="1 (default): fp32-equivalent split-fp16 MFMA (3 x f16 MFMA per product); 0: exact fp32 MFMA; 2: one f16 MFMA per product")
     a = ap.parse_args()
     if a.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if a.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
     rank, world = resolve_job(a.gpus)
     if a.batch > 0:
         WORKLOADS[a.workload] = dict(WORKLOADS[a.workload], B=a.batch)
@@ -694,7 +727,7 @@ def main():
             torch.cuda.synchronize()
 
     sync()
-    sampler = PowerSampler(local).start() if rank == 0 else None
+    sampler = PowerSampler(local).start() if rank == 0 and a.full else None
     t0 = time.perf_counter()
     x = None
     for i in range(a.steps):
@@ -707,14 +740,23 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
 
-    # the ONE data-path collective: per-image PSNR gathered in global image order
-    psnr = psnr_per_image(x, r.clean)
-    if dist_on:
-        psnr = comm(psnr)
-        allp = [torch.empty_like(psnr) for _ in range(world)]
-        dist.all_gather(allp, psnr)
-        psnr = torch.cat(allp)
-    psnr_mean = float(psnr.mean())
+    if a.dump_outputs:
+        xs = x
+        if dist_on:
+            from pnpflow_amd.parallel import gather_in_image_order
+            xs = gather_in_image_order(x.reshape(-1)).view(-1, *x.shape[1:])
+        if rank == 0:
+            dump_outputs(a.dump_outputs, xs)
+
+    if a.full:
+        # the ONE data-path collective: per-image PSNR gathered in global image order
+        psnr = psnr_per_image(x, r.clean)
+        if dist_on:
+            psnr = comm(psnr)
+            allp = [torch.empty_like(psnr) for _ in range(world)]
+            dist.all_gather(allp, psnr)
+            psnr = torch.cat(allp)
+        psnr_mean = float(psnr.mean())
 
     if rank == 0:
         total_images = world * B * a.steps
@@ -733,25 +775,25 @@ def main():
                        "noise": "on-device Philox4x32-10 (one global stream per (iteration, sample), sliced per shard)",
                        "hipgraph": bool(getattr(r.solver, "use_graph", False)), "unet_batch": r.unet_batch(),
                        "parallelism": f"dp{world} (contiguous shards of the global batch, no data-path collective)"},
-            "psnr_db": round(psnr_mean, 4),
-            "power": power,
-            "roofline": conv_roofline(r, a.precision, a.workload, measure_traffic=(world == 1 and not a.no_extra)),
         }
+        if a.full:
+            out.update(psnr_db=round(psnr_mean, 4), power=power,
+                       roofline=conv_roofline(r, a.precision, a.workload, measure_traffic=(world == 1 and not a.no_extra)))
         fpi = r.flops_per_image()
         if fpi:
             out["unet_tflops_end_to_end"] = round(total_images * fpi / dt / 1e12, 2)
         # the boxes of the pool differ by up to 7 % in what their matrix pipe delivers under the power cap, and `value` follows that figure to within 1 % (round 6:
         # 3.17 / 3.30 / 3.40 images/s at probes of 1 703 / 1 759 / 1 825 TFLOP/s): the headline per PFLOP/s of THIS box's measured MFMA ceiling is the
         # number that compares runs on different boxes (not a throughput: `value` is)
-        mc = (out["roofline"].get("mfma_ceiling") or {})
+        mc = (out.get("roofline") or {}).get("mfma_ceiling") or {}
         if world == 1 and mc.get("measured_this_run") and mc.get("tflops_f16_dense"):
             out["roofline"]["mfma_ceiling"]["value_per_box_pflops"] = round(out["value"] / (mc["tflops_f16_dense"] / 1000.0), 4)
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline_ot_ode(wl) if r.is_ode else cpu_baseline(wl)
             except Exception as exc:          # noqa: BLE001   (the reported baseline must not take the measured line with it)
                 out["cpu_baseline"] = {"error": f"{type(exc).__name__}: {exc}"[:400]}
-        if world == 1 and not a.no_extra and a.workload in ("c2_256", "c2"):
+        if a.full and world == 1 and not a.no_extra and a.workload in ("c2_256", "c2"):
             # the other BASELINE configs under the same clock (EXTRA_STEPS full restorations each after a short warm-up that
             # builds the plans / graph), the headline workload in precision mode 2, and the HBM-side numbers of the pointwise
             # prox kernels

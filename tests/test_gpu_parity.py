@@ -1133,12 +1133,36 @@ def test_bench_two_ranks_reproduce_the_single_process_run(hip):
     two ranks restore contiguous halves of a 4-image global batch (global-draw slices, Philox element offset, one gather of
     per-image PSNR); the global PSNR equals the single-process run at batch 4."""
     import json
-    args = ["bench.py", "--workload", "tiny", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-extra"]
+    args = ["bench.py", "--workload", "tiny", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--no-extra"]
     two = json.loads(_torchrun(args + ["--gpus", "2", "--batch", "2"], 2).strip().splitlines()[-1])
     one = json.loads(_torchrun(args + ["--gpus", "1", "--batch", "4"], 1).strip().splitlines()[-1])
     assert two["n_gpus"] == 2 and two["config"]["global_batch"] == 4 and one["config"]["global_batch"] == 4
     assert two["scaling"] == "weak" and two["value"] > 0
     assert abs(two["psnr_db"] - one["psnr_db"]) < 2e-3, (two["psnr_db"], one["psnr_db"])
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(hip, tmp_path):
+    """A plain bench.py run (no --full): the line carries the headline fields and none of the --full measurements, `steps` timed
+    steps make `ms_per_step`, and --dump-outputs writes the last timed step's restored images - the same images again in a second
+    run with the same arguments (same inputs)."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("PNPFLOW_DIST_BACKEND", "WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    outs = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        res = subprocess.run([sys.executable, "bench.py", "--workload", "tiny", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)],
+                             cwd=root, env=env, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-2000:]
+        line = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+        assert all(k in line for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step")), line
+        assert not any(k in line for k in ("psnr_db", "power", "roofline", "cpu_baseline", "configs", "pointwise")), line
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0
+        assert abs(line["value"] * line["ms_per_step"] / 1e3 - 4) < 0.05, line          # 4 images per timed step
+        x = np.load(d / "restored.npy")
+        assert x.dtype == np.float32 and x.shape == (4, 3, 64, 64) and np.isfinite(x).all()
+        outs.append(x)
+    np.testing.assert_allclose(outs[0], outs[1], atol=TRAJ_ATOL)
 
 
 def test_rccl_executes_the_job_collectives_on_one_gpu(hip):
@@ -1150,7 +1174,7 @@ def test_rccl_executes_the_job_collectives_on_one_gpu(hip):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("PNPFLOW_DIST_BACKEND", "WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["MASTER_ADDR"] = "127.0.0.1"
-    args = [sys.executable, "bench.py", "--workload", "tiny", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-extra", "--batch", "4"]
+    args = [sys.executable, "bench.py", "--workload", "tiny", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--no-extra", "--batch", "4"]
     forced = subprocess.run(args + ["--force-dist"], cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert forced.returncode == 0, forced.stderr[-2000:]
     js = [l for l in forced.stdout.splitlines() if l.startswith("{")]

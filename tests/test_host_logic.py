@@ -361,6 +361,23 @@ def test_bench_refuses_a_world_size_that_is_not_gpus():
     assert out.returncode != 0 and "WORLD_SIZE=1" in (out.stderr + out.stdout)
 
 
+def test_bench_dump_outputs_writes_float32_within_its_budget(tmp_path, monkeypatch):
+    """`--dump-outputs DIR`: the restored images as DIR/restored.npy in float32; above the byte budget, the same seeded sample of
+    whole images (in image order) on every call."""
+    import bench
+    x = torch.arange(10 * 3 * 4 * 4, dtype=torch.float32).view(10, 3, 4, 4)
+    bench.dump_outputs(str(tmp_path / "all"), x.double())
+    a = np.load(tmp_path / "all" / "restored.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, x.numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4096 + 4 * x[0].numel() * 4)          # room for 4 of the 10 images
+    for name in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / name), x)
+    s1, s2 = np.load(tmp_path / "s1" / "restored.npy"), np.load(tmp_path / "s2" / "restored.npy")
+    assert s1.dtype == np.float32 and s1.shape == (4, 3, 4, 4) and np.array_equal(s1, s2)
+    idx = (s1[:, 0, 0, 0] / x[0].numel()).astype(int)
+    assert list(idx) == sorted(set(idx)) and all(np.array_equal(s1[j], a[i]) for j, i in enumerate(idx))
+
+
 def test_cv2_line_restatement_known_answers():
     """What OpenCV's thick lines are known for (drawing.cpp ThickLine): an EVEN thickness t covers t + 1 pixel rows (the body is
     p +- round(t/2 * n) in 16.16 fixed point, both borders inclusive), the end caps are filled midpoint circles of radius (t + 1) // 2

@@ -8,7 +8,7 @@ for s in "256 160" "128 160" "256 32"; do
   python tools/layer_summary.py $O/l$1_$2.csv > $O/l$1_$2.txt; head -1 $O/l$1_$2.txt
 done
 WLS="c2_256 c5" NO_PMC=1 bash tools/profile_round.sh r05a > /dev/null 2>&1
-timeout 900 python bench.py --steps 3 --warmup 1 > $O/bench.json 2> $O/bench.err; echo "bench rc $?"
+timeout 900 python bench.py --steps 3 --warmup 1 --full > $O/bench.json 2> $O/bench.err; echo "bench rc $?"
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r05a/bench.json").read().strip().splitlines()[-1])

@@ -2,7 +2,7 @@
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out/r06f; mkdir -p $O
 timeout 1200 python -m pytest tests -m gpu -q > $O/pytest.log 2>&1; echo "pytest rc $?"; tail -4 $O/pytest.log
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench.err; echo "bench rc $?"
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench.err; echo "bench rc $?"
 WLS="c2_256 c2 c5" NO_PMC=1 bash tools/profile_round.sh r06 > /dev/null 2>&1
 bash tools/pmc_level0.sh > /dev/null 2>&1
 python tools/pmc_table.py gpurun_out/pmc_level0 > $O/pmc_conv_counters.md 2>&1
