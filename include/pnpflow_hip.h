@@ -269,6 +269,43 @@ typedef struct pf_ot_ode_params {
 int pf_ot_ode_restore(pf_engine* e, const pf_degradation* d, const pf_ot_ode_params* prm, const float* y, float* x_inout, int B,
                       void* stream, void (*iter_cb)(int iteration, void* user), void* user);
 
+/* ---- D-Flow (pnpflow/methods/d_flow.py) ------------------------------------------------------------------------------------
+ * T(z) = steps_euler - 1 explicit midpoint steps of the velocity net (forward_flow_matching, d_flow.py:41-49):
+ *   z += delta * v(z + delta/2 * v(z, t_i), t_i + delta/2),  t_i = delta * i + start_time,  delta = (1 - start_time) / (steps_euler - 1)
+ * The schedule comes as host fp32 tables computed with the reference's own expressions; the net sees t * the solver time scale
+ * (pf_engine_set_solver_time_scale: 999 for the NCSN++ net). */
+typedef struct pf_d_flow_params {
+    int32_t steps_euler;          /* >= 2 */
+    int32_t use_graph;            /* capture the call into a hipGraph once and replay it while the arguments below stay the same */
+    const float* host_t;          /* host [steps_euler - 1]: t_i */
+    const float* host_t_mid;      /* host [steps_euler - 1]: t_i + delta/2 */
+    float delta;                  /* fp32(delta) */
+    float half_delta;             /* fp32(delta / 2) */
+} pf_d_flow_params;
+/* x_out = T(z); z, x_out: [B,C,H,W] */
+int pf_d_flow_forward(pf_engine* e, const pf_d_flow_params* prm, const float* z, float* x_out, int B, void* stream);
+/* One LBFGS closure of d_flow.py:110-121 at z, per image b:
+ *   loss_per_image[b] = |H(T(z_b)) - y_b|^2 + lmbda (0.5 clamp(|z_b|^2, -1e6, 1e6) - (d-1) log(|z_b| + 1e-5)),  d = C*H*W
+ *   grad = d sum_b loss_per_image[b] / dz   (the hand-written adjoint of T seeded with 2 H_adj(r), plus the regulariser gradient)
+ * The ten evaluation inputs of T are kept; every VJP of the reverse sweep re-runs its forward under the retained plan.  Reductions are
+ * deterministic (fp64 per-block partials, fixed-order finish).  Afterwards the retained forward (pf_unet_backward) is that of (z, t_0).
+ * y: [B,C,Hy,Wy]; loss_per_image: device [B]; grad: [B,C,H,W].  The engine owns the operator scratch. */
+int pf_d_flow_value_and_grad(pf_engine* e, const pf_degradation* d, const pf_d_flow_params* prm, const float* z, const float* y, float lmbda,
+                             float* loss_per_image, float* grad, int B, void* stream);
+
+/* Adaptive Dormand-Prince 5(4) solve of dx/dt = v(x, t) from t0 to t1 (torchdiffeq odeint(method='dopri5') as inverse_flow_matching,
+ * d_flow.py:51-60, calls it with t 1 -> 0): RMS error norm over the whole batch tensor (one step sequence for all images), Hairer's
+ * initial step, FSAL, 4th-order dense output at t1.  Step control runs on the host (one 8-byte read of the error ratio per attempt).
+ * stats (host, may be NULL): [accepted steps, rejected steps, velocity evaluations].  More than max_steps attempts fails with
+ * PF_ERR_NUMERIC and no result.  Synchronises `stream`. */
+typedef struct pf_dopri5_params {
+    double t0, t1;
+    double rtol, atol;
+    int32_t max_steps;
+    int32_t reserved0;
+} pf_dopri5_params;
+int pf_flow_ode_dopri5(pf_engine* e, const pf_dopri5_params* prm, const float* x_in, float* x_out, int B, int64_t* stats, void* stream);
+
 /* ---- whole restoration loop --------------------------------------------------------- */
 typedef struct pf_pnp_params {
     int32_t steps;            /* steps_pnp */

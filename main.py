@@ -132,6 +132,9 @@ def main():
         elif args.method == 'ot_ode':
             from pnpflow_amd.methods.ot_ode import OT_ODE
             method = OT_ODE(model, device, args)
+        elif args.method == 'd_flow':
+            from pnpflow_amd.methods.d_flow import D_FLOW
+            method = D_FLOW(model, device, args)
         else:
             raise ValueError("The method your entered does not exist")
         method.run_method(loaders, degradation, sigma_noise)

@@ -49,6 +49,16 @@ class PfOtOdeParams(C.Structure):
                 ("use_graph", C.c_int32), ("reserved0", C.c_int32), ("host_cb_mask", C.c_void_p)]
 
 
+class PfDFlowParams(C.Structure):
+    _fields_ = [("steps_euler", C.c_int32), ("use_graph", C.c_int32), ("host_t", C.POINTER(C.c_float)), ("host_t_mid", C.POINTER(C.c_float)),
+                ("delta", C.c_float), ("half_delta", C.c_float)]
+
+
+class PfDopri5Params(C.Structure):
+    _fields_ = [("t0", C.c_double), ("t1", C.c_double), ("rtol", C.c_double), ("atol", C.c_double), ("max_steps", C.c_int32),
+                ("reserved0", C.c_int32)]
+
+
 ITER_CB = C.CFUNCTYPE(None, C.c_int, C.c_void_p)
 
 # name -> (restype, argtypes); this table is also what tests use to check that every symbol
@@ -95,6 +105,10 @@ SIGNATURES = {
     "pf_lpips_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "pf_ot_ode_restore": (C.c_int, [C.c_void_p, C.POINTER(PfDegradation), C.POINTER(PfOtOdeParams), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, ITER_CB, C.c_void_p]),
     "pf_pnp_flow_restore": (C.c_int, [C.c_void_p, C.POINTER(PfDegradation), C.POINTER(PfPnpParams), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, ITER_CB, C.c_void_p]),
+    "pf_d_flow_forward": (C.c_int, [C.c_void_p, C.POINTER(PfDFlowParams), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "pf_d_flow_value_and_grad": (C.c_int, [C.c_void_p, C.POINTER(PfDegradation), C.POINTER(PfDFlowParams), C.c_void_p, C.c_void_p, C.c_float,
+                                           C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "pf_flow_ode_dopri5": (C.c_int, [C.c_void_p, C.POINTER(PfDopri5Params), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_void_p]),
     "pf_engine_memory_bytes": (C.c_int64, [C.c_void_p]),
     "pf_engine_check_numerics": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pf_engine_profile": (C.c_int, [C.c_void_p, C.c_int]),

@@ -125,6 +125,8 @@ struct NxMod {                 // one entry of NCSNpp.all_modules (ncsnpp.py:72-
     bool up = false, down = false;
 };
 
+struct DFlowState;                 // D-Flow / dopri5 buffers and graphs (engine_dflow.inc)
+
 struct pf_engine {
     int device = 0;
     pf_unet_cfg cfg{};
@@ -168,6 +170,8 @@ struct pf_engine {
     struct OdeKey { const void* plan; int kind, half, sf, ntaps; const void* mask; const void* taps; int B; float sigma2, delta; int pad_; };   // compared with memcmp: no implicit padding (static_assert below)
     OdeKey okey{}; hipGraph_t ograph = nullptr; hipGraphExec_t ogexec = nullptr;
     hipStream_t work_stream = nullptr;   // used when the caller passes the NULL stream and asks for graph replay
+    DFlowState* dflow = nullptr;         // pf_d_flow_* / pf_flow_ode_dopri5 state (engine_dflow.inc)
+    const void* held_plans[3] = {};      // plans a cached D-Flow graph replays (kept out of the plan cache's eviction)
     // profiling
     bool profile = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
@@ -1107,6 +1111,7 @@ static int build_plan(pf_engine* e, int B, bool retain, Plan** out_plan) {
         auto victim = e->plans.end();
         for (auto jt = e->plans.begin(); jt != e->plans.end(); ++jt) {
             if (jt->second.get() == e->retained_plan || jt->second.get() == e->gkey.plan || jt->second.get() == e->okey.plan) continue;
+            if (jt->second.get() == e->held_plans[0] || jt->second.get() == e->held_plans[1] || jt->second.get() == e->held_plans[2]) continue;
             if (victim == e->plans.end() || jt->second->last_used < victim->second->last_used) victim = jt;
         }
         if (victim == e->plans.end()) break;
@@ -1708,9 +1713,11 @@ int pf_ncsnpp_create(int device_id, const pf_ncsnpp_cfg* cfg, pf_engine** out) {
 
 static void drop_graph(pf_engine* e);
 static void drop_ode_graph(pf_engine* e);
+static void drop_dflow_graphs(pf_engine* e);
+static void free_dflow(pf_engine* e);
 int pf_engine_set_solver_time_scale(pf_engine* e, float scale) {
     if (!e || !(scale > 0.f)) return PF_ERR_INVALID;
-    if (scale != e->solver_time_scale) { drop_graph(e); drop_ode_graph(e); e->solver_time_scale = scale; }   // the captured graphs bake the scale in
+    if (scale != e->solver_time_scale) { drop_graph(e); drop_ode_graph(e); drop_dflow_graphs(e); e->solver_time_scale = scale; }   // the captured graphs bake the scale in
     return PF_OK;
 }
 
@@ -1762,6 +1769,7 @@ void pf_engine_destroy(pf_engine* e) {
     hipSetDevice(e->device);
     drop_graph(e);
     free_ode(e);
+    free_dflow(e);
     for (auto& kv : e->plans) for (void* p : kv.second->allocs) hipFree(p);
     for (void* p : e->weight_allocs) hipFree(p);
     for (auto& ev : e->ev_pool) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
@@ -1816,7 +1824,7 @@ int pf_engine_finalize_weights(pf_engine* e) {
 int pf_engine_set_precision(pf_engine* e, int mode) {
     if (!e) return PF_ERR_INVALID;
     if (mode < 0 || mode > 2) { e->err = "precision mode must be 0 (fp32 MFMA), 1 (split-fp16 MFMA, fp32-equivalent) or 2 (single fp16 MFMA)"; return PF_ERR_INVALID; }
-    if (mode != e->precision) { drop_graph(e); drop_ode_graph(e); }       // captured graphs bake the kernel choice in
+    if (mode != e->precision) { drop_graph(e); drop_ode_graph(e); drop_dflow_graphs(e); }       // captured graphs bake the kernel choice in
     e->precision = mode;
     return PF_OK;
 }
@@ -2298,3 +2306,5 @@ int pf_engine_profile_read(pf_engine* e, int64_t* launches, double* ms_conv_gemm
 }
 
 }  // extern "C"
+
+#include "engine_dflow.inc"

@@ -275,6 +275,23 @@ hipError_t launch_ot_ode_vec_blur(const DegView& d, const float* x, const float*
 hipError_t launch_ot_ode_update(float* x, const float* vt, const float* vec, const float* g, const float* one_minus_t, const float* coef,
                                 float delta, int B, int n, hipStream_t s);
 
+// ---- D-Flow and dopri5 glue (flow_solvers.hip) --------------------------------------------------------------------------------
+struct RkTerms { const float* k[7]; float c[7]; int n; };     // sum_j c[j] * k[j], j < n
+int reduction_parts(int64_t n4);     // fp64 partial sums per image (D-Flow) / per tensor (dopri5 norm) for n4 float4 lanes
+hipError_t launch_dflow_axpy(const float* z, const float* v, float* out, float c, int64_t n, hipStream_t s);
+// loss[b] = |hx_b - y_b|^2 + lmbda reg(z_b), coef[b] = d reg/dz_b / z_b, r2 = 2 (hx - y); partial: >= 2 * B * 64 doubles
+hipError_t launch_dflow_objective(const float* hx, const float* y, float* r2, const float* z, double* partial, float* loss, float* coef, float lmbda,
+                                  int B, int64_t ny, int64_t n, hipStream_t s);
+hipError_t launch_dflow_reg_grad(const float* g, const float* z, const float* coef, float lmbda, float* grad, int B, int64_t n, hipStream_t s);
+hipError_t launch_dflow_scale(const float* jg, float* h, float delta, int64_t n, hipStream_t s);
+hipError_t launch_dflow_adjoint(float* g, const float* h, const float* jh, float half_delta, int64_t n, hipStream_t s);
+hipError_t launch_rk_combine(const float* y0, const RkTerms& t, float* out, int64_t n, hipStream_t s);
+// out[0] = sum over the whole tensor of (e / (atol + rtol max(|y0|, |y1|)))^2; partial: >= 64 doubles
+hipError_t launch_rk_norm(const float* a, const float* b, const float* y0, const float* y1, const RkTerms& err, float atol, float rtol, double* partial,
+                          double* out, int64_t n, hipStream_t s);
+hipError_t launch_rk_interp(const float* y0, const float* y1, const float* ymid, const float* k0, const float* k6, float sign, float dt, float x, float* out,
+                            int64_t n, hipStream_t s);
+
 // ---- NCSN++ ("rectified") velocity net, the ops that are not convs (ncsnpp_ops.hip) ----------------------------------------
 // FIR resampling of an NHWC activation (upfirdn2d of up_or_down_sampling.py:204-259 on every channel), optionally of TWO views of
 // the same source in one pass: `out_act` takes act(GroupNorm(src)) (the per-image sc/sh of `coef`, SiLU), `out_raw` the raw
