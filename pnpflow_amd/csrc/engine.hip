@@ -18,6 +18,7 @@
 
 #include "../../include/pnpflow_hip.h"
 #include "pf_common.h"
+#include "weight_pack.h"
 
 using namespace pf;
 
@@ -45,6 +46,7 @@ struct Op {
     OpKind kind;
     ConvParams cp; int stride = 1, up = 0;
     int dma = 0;                                    // OP_CONV: 1 = conv_dma.hip (its operands were written by the OP_PREP in front of it)
+    int terms = 0;                                  // OP_CONV: conv_terms() of the plan's precision mode - the TERMS form that matches the weight images chosen at build time
     int use_pp = 0; PPParams ppp{};                 // OP_CONV: 1 = conv_pp.hip (persistent two-team kernel of the 32-channel level), 2 = conv_sp.hip (64- / 128-channel levels)
     PrepParams pp{};
     EdgeConvParams ep;
@@ -313,210 +315,52 @@ static int build_arch(pf_engine* e) {
 // --------------------------------------------------------------------------------------
 static const HostTensor& W(pf_engine* e, const std::string& n) { return e->host.at(n); }
 
-static float* upload(pf_engine* e, const std::string& key, const std::vector<float>& v) {
-    auto it = e->dev.find(key);
-    if (it != e->dev.end()) return it->second;
+// the one allocation + copy of a weight array not yet in e->dev (16-byte minimum, counted in e->bytes); nothing is inserted when the allocation fails
+static float* upload_new(pf_engine* e, const std::string& key, const void* src, size_t bytes) {
     float* d = nullptr;
-    if (hipMalloc(&d, std::max<size_t>(v.size(), 4) * sizeof(float)) != hipSuccess) return nullptr;
-    e->bytes += (int64_t)(std::max<size_t>(v.size(), 4) * sizeof(float));
-    hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (hipMalloc(&d, std::max<size_t>(bytes, 16)) != hipSuccess) return nullptr;
+    e->bytes += (int64_t)std::max<size_t>(bytes, 16);
+    hipMemcpy(d, src, bytes, hipMemcpyHostToDevice);
     e->weight_allocs.push_back(d);
     e->dev[key] = d;
     return d;
 }
-
-// OIHW conv weight, input channels [lo,hi) -> fragment-major [chunk][tap][kstep(2)][Cout][8]
-// (zero padded K tail): the B fragment of one wave (32 channels x 8 k) is contiguous.
-static float* packed_conv(pf_engine* e, const std::string& wname, int lo, int hi) {
-    const std::string key = wname + "#" + std::to_string(lo) + ":" + std::to_string(hi);
+static float* upload(pf_engine* e, const std::string& key, const std::vector<float>& v) {
     auto it = e->dev.find(key);
-    if (it != e->dev.end()) return it->second;
-    const HostTensor& t = W(e, wname);
-    const int O = (int)t.shape[0], I = (int)t.shape[1], kk = (int)(t.shape[2] * t.shape[3]);
-    const int C = hi - lo, nchunk = (C + CONV_KC - 1) / CONV_KC;
-    std::vector<float> out((size_t)nchunk * kk * O * CONV_KC, 0.f);
-    for (int chn = 0; chn < nchunk; ++chn)
-        for (int tap = 0; tap < kk; ++tap)
-            for (int n = 0; n < O; ++n)
-                for (int k = 0; k < CONV_KC; ++k) {
-                    const int c = chn * CONV_KC + k;
-                    if (c < C)
-                        out[((((size_t)chn * kk + tap) * 2 + k / 8) * O + n) * 8 + k % 8] = t.data[((size_t)n * I + lo + c) * kk + tap];
-                }
-    return upload(e, key, out);
+    return it != e->dev.end() ? it->second : upload_new(e, key, v.data(), v.size() * sizeof(float));
 }
 
-// split-fp16 repack of the same slice: [chunk][tap][hi | lo][Cout][16] halfs, values pre-scaled by 2^8
-static const void* packed_conv16(pf_engine* e, const std::string& wname, int lo, int hi) {
-    const std::string key = wname + "#h" + std::to_string(lo) + ":" + std::to_string(hi);
+static wpack::Oihw oihw(pf_engine* e, const std::string& wname) {
+    const HostTensor& t = W(e, wname);
+    return {t.data.data(), (int)t.shape[0], (int)t.shape[1], (int)(t.shape[2] * t.shape[3])};
+}
+static std::string range_key(int lo, int hi) { return std::to_string(lo) + ":" + std::to_string(hi); }
+
+// Every packed weight image reaches the device through here: cache lookup under `key`, the packer of weight_pack.h (`pack`: () -> vector, run on a
+// miss only), upload of its bytes and - for the images attach_dma / attach_pp derive further images from - the record of the host slice it came from.
+template <class Pack>
+static float* weight_image(pf_engine* e, const std::string& key, Pack pack, const pf_engine::W16Src* src = nullptr) {
     auto it = e->dev.find(key);
     if (it != e->dev.end()) return it->second;
-    const HostTensor& t = W(e, wname);
-    const int O = (int)t.shape[0], I = (int)t.shape[1], kk = (int)(t.shape[2] * t.shape[3]);
-    const int C = hi - lo, nchunk = (C + CONV_KC - 1) / CONV_KC;
-    std::vector<_Float16> out((size_t)nchunk * kk * O * 32, (_Float16)0.f);
-    for (int chn = 0; chn < nchunk; ++chn)
-        for (int tap = 0; tap < kk; ++tap)
-            for (int n = 0; n < O; ++n)
-                for (int k = 0; k < CONV_KC; ++k) {
-                    const int c = chn * CONV_KC + k;
-                    if (c >= C) continue;
-                    const float w = t.data[((size_t)n * I + lo + c) * kk + tap] * 256.0f;
-                    const _Float16 h = (_Float16)w;
-                    const _Float16 l = (_Float16)(w - (float)h);
-                    // block (16-channel slice, tap) = [hi halves: Cout x 16][lo halves: Cout x 16]: the hi (lo) fragment load of a wave
-                    // (32 output channels x 32 B) is ONE contiguous 1 KiB run - with hi and lo interleaved per output channel every
-                    // fragment load touched 2 KiB of half-used lines (round 3: the texture addresser is the busiest unit of the
-                    // 32-channel level, profiles/r03_pmc_level0_counters.md)
-                    const size_t blk = ((size_t)chn * kk + tap) * O * 32;
-                    out[blk + (size_t)n * 16 + k] = h; out[blk + (size_t)O * 16 + (size_t)n * 16 + k] = l;
-                }
-    std::vector<float> raw(out.size() / 2);
-    memcpy(raw.data(), out.data(), out.size() * sizeof(_Float16));
-    const void* d = upload(e, key, raw);
-    if (d) e->w16_src[d] = {wname, lo, hi};
+    const auto img = pack();
+    float* d = upload_new(e, key, img.data(), img.size() * sizeof(img[0]));
+    if (d && src) e->w16_src[d] = *src;
     return d;
 }
 
-// hi-only repack of the same slice for the single-term (precision mode 2) LDS-DMA kernel: [slice16][tap][Cout][16 halfs], values
-// pre-scaled by 2^8 like the split repack (so that the epilogue's 2^-8 is shared) - no low halves are stored, fetched or multiplied
-static const void* packed_conv16h(pf_engine* e, const std::string& wname, int lo, int hi) {
-    const std::string key = wname + "#h1_" + std::to_string(lo) + ":" + std::to_string(hi);
-    auto it = e->dev.find(key);
-    if (it != e->dev.end()) return it->second;
-    const HostTensor& t = W(e, wname);
-    const int O = (int)t.shape[0], I = (int)t.shape[1], kk = (int)(t.shape[2] * t.shape[3]);
-    const int C = hi - lo, nchunk = (C + CONV_KC - 1) / CONV_KC;
-    std::vector<_Float16> out((size_t)nchunk * kk * O * 16, (_Float16)0.f);
-    for (int chn = 0; chn < nchunk; ++chn)
-        for (int tap = 0; tap < kk; ++tap)
-            for (int n = 0; n < O; ++n)
-                for (int k = 0; k < CONV_KC; ++k) {
-                    const int c = chn * CONV_KC + k;
-                    if (c >= C) continue;
-                    out[(((size_t)chn * kk + tap) * O + n) * 16 + k] = (_Float16)(t.data[((size_t)n * I + lo + c) * kk + tap] * 256.0f);
-                }
-    std::vector<float> raw((out.size() + 1) / 2);
-    memcpy(raw.data(), out.data(), out.size() * sizeof(_Float16));
-    return upload(e, key, raw);
+// images of input channels [lo, hi) of the OIHW host tensor `wname` (layouts: weight_pack.h): fragment-major fp32 / 16-channel-slice fp16, split (terms 3)
+// or hi-only (terms 1)
+static float* packed_conv(pf_engine* e, const std::string& wname, int lo, int hi) {
+    return weight_image(e, wname + "#" + range_key(lo, hi), [&] { return wpack::frag32(oihw(e, wname), lo, hi); });
+}
+static const void* packed_conv16(pf_engine* e, const std::string& wname, int lo, int hi, int terms = 3) {
+    const pf_engine::W16Src src{wname, lo, hi};
+    return weight_image(e, wname + (terms == 1 ? "#h1_" : "#h") + range_key(lo, hi), [&] { return wpack::slice16(oihw(e, wname), lo, hi, terms); }, terms == 1 ? nullptr : &src);
 }
 
-// LDS weight image of ONE 32-channel K-chunk for conv_pp.hip (Cout = 32): [k16-step s = tap * 2 + j][hi | lo][k-half][column][8 halfs], channel of
-// (s, k-half, i) = lo + j * 16 + k-half * 8 + i; the same x 2^8 pre-scale and hi / lo split as packed_conv16, so the products are the same
-static const void* packed_conv_pp(pf_engine* e, const std::string& wname, int lo) {
-    const std::string key = wname + "#pp" + std::to_string(lo);
-    auto it = e->dev.find(key);
-    if (it != e->dev.end()) return it->second;
-    const HostTensor& t = W(e, wname);
-    const int O = (int)t.shape[0], I = (int)t.shape[1], kk = (int)(t.shape[2] * t.shape[3]);
-    std::vector<_Float16> out((size_t)kk * 2 * 2 * 2 * O * 8, (_Float16)0.f);
-    for (int tap = 0; tap < kk; ++tap)
-        for (int j = 0; j < 2; ++j)
-            for (int kh = 0; kh < 2; ++kh)
-                for (int n = 0; n < O; ++n)
-                    for (int i = 0; i < 8; ++i) {
-                        const int c = lo + j * 16 + kh * 8 + i;
-                        const int oc = 4 * (n & 7) + (n >> 3);      // MFMA column n = 8 g + k carries output channel 4 k + g (conv_pp.hip's epilogue transpose)
-                        const float w = t.data[((size_t)oc * I + c) * kk + tap] * 256.0f;
-                        const _Float16 h = (_Float16)w;
-                        const _Float16 l = (_Float16)(w - (float)h);
-                        const size_t blk = (size_t)(tap * 2 + j) * 2 * (2 * O * 8);
-                        out[blk + ((size_t)kh * O + n) * 8 + i] = h;
-                        out[blk + (size_t)2 * O * 8 + ((size_t)kh * O + n) * 8 + i] = l;
-                    }
-    std::vector<float> raw(out.size() / 2);
-    memcpy(raw.data(), out.data(), out.size() * sizeof(_Float16));
-    return upload(e, key, raw);
-}
-
-// LDS weight image of ONE 16-channel K-chunk for conv_sp.hip at Cout = 64 (3x3): [tap][hi | lo][N-tile][k-half][column][8 halfs], input channel
-// of (k-half, i) = lo + k-half * 8 + i, output channel of (N-tile, column n) = 32 N-tile + 4 (n & 7) + (n >> 3); same x 2^8 pre-scale and split
-static const void* packed_conv_sp64(pf_engine* e, const std::string& wname, int lo) {
-    const std::string key = wname + "#sp64_" + std::to_string(lo);
-    auto it = e->dev.find(key);
-    if (it != e->dev.end()) return it->second;
-    const HostTensor& t = W(e, wname);
-    const int O = (int)t.shape[0], I = (int)t.shape[1], kk = (int)(t.shape[2] * t.shape[3]);
-    if (O != 64 || kk != 9) return nullptr;
-    std::vector<_Float16> out((size_t)9 * 2 * 2 * 2 * 32 * 8, (_Float16)0.f);
-    for (int tap = 0; tap < 9; ++tap)
-        for (int nt = 0; nt < 2; ++nt)
-            for (int kh = 0; kh < 2; ++kh)
-                for (int n = 0; n < 32; ++n)
-                    for (int i = 0; i < 8; ++i) {
-                        const int c = lo + kh * 8 + i;
-                        const int oc = 32 * nt + 4 * (n & 7) + (n >> 3);
-                        const float w = t.data[((size_t)oc * I + c) * 9 + tap] * 256.0f;
-                        const _Float16 h = (_Float16)w;
-                        const _Float16 l = (_Float16)(w - (float)h);
-                        const size_t inner = ((size_t)kh * 32 + n) * 8 + i;
-                        out[(((size_t)tap * 2 + 0) * 2 + nt) * 512 + inner] = h;
-                        out[(((size_t)tap * 2 + 1) * 2 + nt) * 512 + inner] = l;
-                    }
-    std::vector<float> raw(out.size() / 2);
-    memcpy(raw.data(), out.data(), out.size() * sizeof(_Float16));
-    return upload(e, key, raw);
-}
-
-// LDS weight image of ONE 16-channel K-chunk for conv_sp.hip at Cout = 128 (3x3): [tap][hi | lo][N-tile 0..3][k-half][column][8 halfs] = 9 tap
-// slots of 8 KiB; input channel of (k-half, i) = lo + k-half * 8 + i, output channel of (N-tile, column n) = 32 N-tile + 4 (n & 7) + (n >> 3);
-// same x 2^8 pre-scale and split as packed_conv16
-static const void* packed_conv_sp128(pf_engine* e, const std::string& wname, int lo) {
-    const std::string key = wname + "#sp128_" + std::to_string(lo);
-    auto it = e->dev.find(key);
-    if (it != e->dev.end()) return it->second;
-    const HostTensor& t = W(e, wname);
-    const int O = (int)t.shape[0], I = (int)t.shape[1], kk = (int)(t.shape[2] * t.shape[3]);
-    if (O != 128 || kk != 9) return nullptr;
-    std::vector<_Float16> out((size_t)9 * 2 * 4 * 512, (_Float16)0.f);
-    for (int tap = 0; tap < 9; ++tap)
-        for (int nt = 0; nt < 4; ++nt)
-            for (int kh = 0; kh < 2; ++kh)
-                for (int n = 0; n < 32; ++n)
-                    for (int i = 0; i < 8; ++i) {
-                        const int c = lo + kh * 8 + i;
-                        const int oc = 32 * nt + 4 * (n & 7) + (n >> 3);
-                        const float w = t.data[((size_t)oc * I + c) * 9 + tap] * 256.0f;
-                        const _Float16 h = (_Float16)w;
-                        const _Float16 l = (_Float16)(w - (float)h);
-                        const size_t inner = ((size_t)kh * 32 + n) * 8 + i;
-                        out[(((size_t)tap * 2 + 0) * 4 + nt) * 512 + inner] = h;
-                        out[(((size_t)tap * 2 + 1) * 4 + nt) * 512 + inner] = l;
-                    }
-    std::vector<float> raw(out.size() / 2);
-    memcpy(raw.data(), out.data(), out.size() * sizeof(_Float16));
-    return upload(e, key, raw);
-}
-
-// hi-only image of the same chunk for conv_sp's TERMS = 1 form (precision mode 2): [tap][N-tile][k-half][column][8 halfs] = 9 taps of NT KiB, values
-// RNE16(w x 2^8) - the hi halves of the images above, i.e. the weights conv_mfma16's TERMS = 1 form multiplies with
-static const void* packed_conv_sp_h(pf_engine* e, const std::string& wname, int lo, int cout) {
-    const std::string key = wname + "#sph" + std::to_string(cout) + "_" + std::to_string(lo);
-    auto it = e->dev.find(key);
-    if (it != e->dev.end()) return it->second;
-    const HostTensor& t = W(e, wname);
-    const int O = (int)t.shape[0], I = (int)t.shape[1], kk = (int)(t.shape[2] * t.shape[3]);
-    if (O != cout || (cout != 64 && cout != 128) || kk != 9) return nullptr;
-    const int NT = cout / 32;
-    std::vector<_Float16> out((size_t)9 * NT * 512, (_Float16)0.f);
-    for (int tap = 0; tap < 9; ++tap)
-        for (int nt = 0; nt < NT; ++nt)
-            for (int kh = 0; kh < 2; ++kh)
-                for (int n = 0; n < 32; ++n)
-                    for (int i = 0; i < 8; ++i) {
-                        const int c = lo + kh * 8 + i;
-                        const int oc = 32 * nt + 4 * (n & 7) + (n >> 3);
-                        out[((size_t)tap * NT + nt) * 512 + ((size_t)kh * 32 + n) * 8 + i] = (_Float16)(t.data[((size_t)oc * I + c) * 9 + tap] * 256.0f);
-                    }
-    std::vector<float> raw(out.size() / 2);
-    memcpy(raw.data(), out.data(), out.size() * sizeof(_Float16));
-    return upload(e, key, raw);
-}
-
-static void fill_packed_seg(ConvSeg& s, const float* w, int taps, int Cout) {
-    (void)taps; (void)Cout;
-    s.w = w; s.w_mode = 0; s.w_bs = 0; s.w_cs = 0; s.w_ts = 0; s.w_ns = 0; s.w_ks = 0; s.w16 = nullptr;
-}
+// the kernels' TERMS of this engine's precision mode, fixed when a plan is built (plans are keyed by the mode): 0 = exact fp32 MFMA, 3 = split-fp16
+// (hi and lo images), 1 = single fp16 product (hi-only images where one exists).  Chooses the weight image AND, through Op::terms, the kernel form.
+static int conv_terms(const pf_engine* e) { return e->precision == 0 ? 0 : e->precision == 2 ? 1 : 3; }
 
 // --------------------------------------------------------------------------------------
 // plan construction
@@ -558,6 +402,12 @@ static ConvParams base_params(int B, int H, int W, int Hs, int Ws, const Tensor&
 static void add_seg(ConvParams& p, const Tensor& t, int xform, int taps, int gn_off) {
     ConvSeg& s = p.seg[p.nseg++];
     s.src = t.p; s.C = t.C; s.cstride = t.C; s.coff = 0; s.xform = xform; s.taps = taps; s.gn_off = gn_off; s.stats = t.stats;
+}
+// K-segment over input channels [lo, hi) of the packed conv weight `wname`: its fp32 and its split-fp16 image (both are uploaded in every mode)
+static void packed_seg(pf_engine* e, ConvParams& p, const Tensor& t, int xform, int taps, int gn_off, const std::string& wname, int lo, int hi) {
+    add_seg(p, t, xform, taps, gn_off);
+    ConvSeg& s = p.seg[p.nseg - 1];
+    s.w = packed_conv(e, wname, lo, hi); s.w_mode = 0; s.w16 = packed_conv16(e, wname, lo, hi);
 }
 
 // GroupNorm coefficients (and, in the split-fp16 mode, the power-of-two operand scale) of a conv launch are finalised by a
@@ -601,14 +451,14 @@ static ConvParams with_coef(Builder& bd, ConvParams p, std::vector<Op>& ops) {
 // (after the OP_GN_COEF that finalises its GroupNorm coefficients / operand scales).  The a16 buffers are launch-local temporaries.
 static bool attach_dma(Builder& bd, ConvParams& p, int stride, int up, std::vector<Op>& ops) {
     pf_engine* e = bd.e;
-    if (e->precision == 0) return false;
-    const int terms = e->precision == 2 ? 1 : 3;
+    const int terms = conv_terms(e);
+    if (terms == 0) return false;
     if (terms == 1)
         for (int i = 0; i < p.nseg; ++i) {
             auto it = e->w16_src.find(p.seg[i].w16);
             if (p.seg[i].w_mode != 0 || it == e->w16_src.end()) return false;
             if ((it->second.hi - it->second.lo) % 64 != 0) return false;
-            p.seg[i].w16h = packed_conv16h(e, it->second.name, it->second.lo, it->second.hi);
+            p.seg[i].w16h = packed_conv16(e, it->second.name, it->second.lo, it->second.hi, 1);
         }
     if (!conv_dma_supported(p, stride, up, terms)) return false;
     Op op{}; op.kind = OP_PREP;
@@ -633,9 +483,9 @@ static bool attach_dma(Builder& bd, ConvParams& p, int stride, int up, std::vect
 // levels: 16-channel K-chunks, weights streamed through LDS slots): the launch becomes a list of K-chunks in the kernel argument
 static int attach_pp(Builder& bd, const ConvParams& p, int stride, int up, PPParams& q) {      // 0: no; 1: conv_pp; 2: conv_sp
     pf_engine* e = bd.e;
-    if (e->precision == 0) return 0;
     // precision mode 2 (one MFMA per product): the hi-only TERMS = 1 forms of both persistent kernels (round 6)
-    const int terms = e->precision == 2 ? 1 : 3;
+    const int terms = conv_terms(e);
+    if (terms == 0) return 0;
     const bool sp = (p.Cout == 128 || p.Cout == 64) && conv_sp_supported(p, stride, up, terms);
     if (!sp && !(p.Cout == 32 && conv_pp_supported(p, stride, up, terms))) return 0;
     q = PPParams{};
@@ -650,9 +500,12 @@ static int attach_pp(Builder& bd, const ConvParams& p, int stride, int up, PPPar
             PPChunk& k = q.ch[n++];
             k.src = sg.src; k.cstride = sg.cstride; k.coff = sg.coff + cc * kc; k.xform = sg.xform;
             k.gn_c0 = sg.gn_off + cc * kc; k.seg = i;
-            k.wimg = !sp ? packed_conv_pp(e, it->second.name, it->second.lo + cc * kc)
-                     : terms == 1 ? packed_conv_sp_h(e, it->second.name, it->second.lo + cc * kc, p.Cout)
-                     : p.Cout == 128 ? packed_conv_sp128(e, it->second.name, it->second.lo + cc * kc) : packed_conv_sp64(e, it->second.name, it->second.lo + cc * kc);
+            // LDS image of this chunk (weight_pack.h): conv_pp reads the split image in both modes, conv_sp the hi-only one at terms 1
+            const std::string& wn = it->second.name; const int lo = it->second.lo + cc * kc;
+            const wpack::Oihw w = oihw(e, wn);
+            if (w.O != p.Cout || (sp && w.kk != 9)) return 0;
+            k.wimg = !sp ? weight_image(e, wn + "#pp" + std::to_string(lo), [&] { return wpack::chunk_pp(w, lo); })
+                         : weight_image(e, wn + (terms == 1 ? "#sph" : "#sp") + std::to_string(p.Cout) + "_" + std::to_string(lo), [&] { return wpack::chunk_sp(w, lo, p.Cout / 32, terms); });
             if (!k.wimg) return 0;
             (sg.taps == 9 ? q.n9 : q.n1) += 1;
         }
@@ -665,7 +518,7 @@ static int attach_pp(Builder& bd, const ConvParams& p, int stride, int up, PPPar
 
 static void push_conv(Builder& bd, const ConvParams& p0, int stride = 1, int up = 0) {
     ConvParams p = with_coef(bd, p0, bd.plan->ops);
-    Op op{}; op.kind = OP_CONV;
+    Op op{}; op.kind = OP_CONV; op.terms = conv_terms(bd.e);
     op.use_pp = attach_pp(bd, p, stride, up, op.ppp);
     op.dma = (!op.use_pp && attach_dma(bd, p, stride, up, bd.plan->ops)) ? 1 : 0;
     op.cp = p; op.stride = stride; op.up = up; op.flops = conv_flops(p);
@@ -681,14 +534,8 @@ static Tensor res_block(Builder& bd, const ResDesc& r, const Tensor& in0, const 
     Tensor h1 = bd.make(r.cout, H, Wd, true);
     {
         ConvParams p = base_params(B, H, Wd, H, Wd, h1);
-        add_seg(p, in0, 2, 9, 0);
-        fill_packed_seg(p.seg[0], packed_conv(e, r.prefix + "conv1.weight", 0, in0.C), 9, r.cout);
-        p.seg[0].w16 = packed_conv16(e, r.prefix + "conv1.weight", 0, in0.C);
-        if (in1) {
-            add_seg(p, *in1, 2, 9, in0.C);
-            fill_packed_seg(p.seg[1], packed_conv(e, r.prefix + "conv1.weight", in0.C, cin), 9, r.cout);
-            p.seg[1].w16 = packed_conv16(e, r.prefix + "conv1.weight", in0.C, cin);
-        }
+        packed_seg(e, p, in0, 2, 9, 0, r.prefix + "conv1.weight", 0, in0.C);
+        if (in1) packed_seg(e, p, *in1, 2, 9, in0.C, r.prefix + "conv1.weight", in0.C, cin);
         p.gn_C = cin; p.gn_cpg = cin / 32;
         p.gamma = upload(e, r.prefix + "norm1.weight", W(e, r.prefix + "norm1.weight").data);
         p.beta = upload(e, r.prefix + "norm1.bias", W(e, r.prefix + "norm1.bias").data);
@@ -699,23 +546,15 @@ static Tensor res_block(Builder& bd, const ResDesc& r, const Tensor& in0, const 
     Tensor out = bd.make(r.cout, H, Wd, true);
     {
         ConvParams p = base_params(B, H, Wd, H, Wd, out);
-        add_seg(p, h1, 2, 9, 0);
-        fill_packed_seg(p.seg[0], packed_conv(e, r.prefix + "conv2.weight", 0, r.cout), 9, r.cout);
-        p.seg[0].w16 = packed_conv16(e, r.prefix + "conv2.weight", 0, r.cout);
+        packed_seg(e, p, h1, 2, 9, 0, r.prefix + "conv2.weight", 0, r.cout);
         p.gn_C = r.cout; p.gn_cpg = r.cout / 32;
         p.gamma = upload(e, r.prefix + "norm2.weight", W(e, r.prefix + "norm2.weight").data);
         p.beta = upload(e, r.prefix + "norm2.bias", W(e, r.prefix + "norm2.bias").data);
         std::vector<float> bias = W(e, r.prefix + "conv2.bias").data;
         if (cin != r.cout) {
             const std::string sw = r.prefix + "shortcut.weight";
-            add_seg(p, in0, 0, 1, 0);
-            fill_packed_seg(p.seg[p.nseg - 1], packed_conv(e, sw, 0, in0.C), 1, r.cout);
-            p.seg[p.nseg - 1].w16 = packed_conv16(e, sw, 0, in0.C);
-            if (in1) {
-                add_seg(p, *in1, 0, 1, 0);
-                fill_packed_seg(p.seg[p.nseg - 1], packed_conv(e, sw, in0.C, cin), 1, r.cout);
-                p.seg[p.nseg - 1].w16 = packed_conv16(e, sw, in0.C, cin);
-            }
+            packed_seg(e, p, in0, 0, 1, 0, sw, 0, in0.C);
+            if (in1) packed_seg(e, p, *in1, 0, 1, 0, sw, in0.C, cin);
             const auto& sb = W(e, r.prefix + "shortcut.bias").data;
             for (size_t i = 0; i < bias.size(); ++i) bias[i] += sb[i];
         } else {
@@ -793,9 +632,7 @@ static Tensor attn_block(Builder& bd, const std::string& pfx, const Tensor& x, i
     Tensor qkv = bd.make(3 * C, H, Wd, false);
     {
         ConvParams p = base_params(B, H, Wd, H, Wd, qkv);
-        add_seg(p, x, 1, 1, 0);
-        fill_packed_seg(p.seg[0], e->dev.at(key + ".w"), 1, 3 * C);
-        p.seg[0].w16 = packed_conv16(e, key + ".w", 0, C);
+        packed_seg(e, p, x, 1, 1, 0, key + ".w", 0, C);
         p.gn_C = C; p.gn_cpg = C / groups;
         p.gamma = upload(e, pfx + "norm.weight", W(e, pfx + "norm.weight").data);
         p.beta = upload(e, pfx + "norm.bias", W(e, pfx + "norm.bias").data);
@@ -853,9 +690,7 @@ static Tensor attn_block(Builder& bd, const std::string& pfx, const Tensor& x, i
     Tensor out = bd.make(C, H, Wd, true);
     {
         ConvParams p = base_params(B, H, Wd, H, Wd, out);
-        add_seg(p, o, 0, 1, 0);
-        fill_packed_seg(p.seg[0], packed_conv(e, pfx + "proj_out.weight", 0, C), 1, C);
-        p.seg[0].w16 = packed_conv16(e, pfx + "proj_out.weight", 0, C);
+        packed_seg(e, p, o, 0, 1, 0, pfx + "proj_out.weight", 0, C);
         if (s_out == 1.0f) {
             p.addvec = upload(e, pfx + "proj_out.bias", W(e, pfx + "proj_out.bias").data);
         } else {
@@ -880,40 +715,30 @@ static Tensor attn_block(Builder& bd, const std::string& pfx, const Tensor& x, i
 // 2i + dy + 1, i.e. source rows {i-1, i, i} for dy = 0 and {i, i, i+1} for dy = 1 (columns alike) - a 2 x 2 conv of the SOURCE image per phase whose
 // tap (ty, tx) carries the sum of the 3 x 3 weights that read the same source pixel: rows R(0,0) = {0}, R(0,1) = {1,2}, R(1,0) = {0,1}, R(1,1) = {2}.
 // 16 instead of 36 multiply-adds per source pixel.  Host tensor [phase * Cout + oc][c][ty * 2 + tx] (sums in double, rounded once to fp32), registered
-// under `wname + "#phase"` so that the ordinary packers (packed_conv16 / packed_conv16h) build its images.
+// under `wname + "#phase"` so that the ordinary packers build its images (sums: wpack::phase_sums).
 static std::string phase_weight(pf_engine* e, const std::string& wname) {
     const std::string key = wname + "#phase";
     if (e->host.count(key)) return key;
-    const HostTensor& t = W(e, wname);
-    const int O = (int)t.shape[0], I = (int)t.shape[1];
-    HostTensor ph; ph.shape = {4 * O, I, 2, 2}; ph.data.assign((size_t)4 * O * I * 4, 0.f); ph.loaded = true;
-    static const int R0[2][2] = {{0, 1}, {0, 2}}, R1[2][2] = {{1, 3}, {2, 3}};      // [d][t] -> first / one-past-last 3x3 index:  d = 0: {0}, {1,2};  d = 1: {0,1}, {2}
-    for (int dy = 0; dy < 2; ++dy) for (int dx = 0; dx < 2; ++dx)
-        for (int oc = 0; oc < O; ++oc) for (int c = 0; c < I; ++c)
-            for (int ty = 0; ty < 2; ++ty) for (int tx = 0; tx < 2; ++tx) {
-                double sum = 0.0;
-                for (int ky = R0[dy][ty]; ky < R1[dy][ty]; ++ky)
-                    for (int kx = R0[dx][tx]; kx < R1[dx][tx]; ++kx) sum += (double)t.data[((size_t)oc * I + c) * 9 + ky * 3 + kx];
-                ph.data[(((size_t)(dy * 2 + dx) * O + oc) * I + c) * 4 + ty * 2 + tx] = (float)sum;
-            }
+    const wpack::Oihw w = oihw(e, wname);
+    HostTensor ph; ph.shape = {4 * w.O, w.I, 2, 2}; ph.data = wpack::phase_sums(w); ph.loaded = true;
     e->host[key] = std::move(ph);
     return key;
 }
 
 // the upsampling conv on conv_dma's UP = 2 form, when the shape qualifies (split-fp16 modes only; the exact-fp32 mode and small / ragged sizes keep
 // the 9-tap form on the upsampled view)
-static bool push_conv_up_phase(Builder& bd, const ConvParams& p9, const std::string& wname) {
+static bool push_conv_up_phase(Builder& bd, const ConvParams& p0, const Tensor& x, const std::string& wname) {      // p0: the launch without its K-segment
     pf_engine* e = bd.e;
-    if (e->precision == 0) return false;
-    const int terms = e->precision == 2 ? 1 : 3;
-    ConvParams q = p9;
+    const int terms = conv_terms(e);
+    if (terms == 0) return false;
+    ConvParams q = p0;
+    add_seg(q, x, 0, 4, 0);
     ConvSeg& sg = q.seg[0];
     if (!conv_dma_phase_shape_ok(q, terms)) return false;      // (before any weight image is built)
-    const std::string key = phase_weight(e, wname);
-    sg.taps = 4; sg.w = nullptr; sg.w16 = packed_conv16(e, key, 0, sg.C);
+    sg.w16 = packed_conv16(e, phase_weight(e, wname), 0, sg.C);
     if (!sg.w16) return false;
     ConvParams p = with_coef(bd, q, bd.plan->ops);
-    Op op{}; op.kind = OP_CONV;
+    Op op{}; op.kind = OP_CONV; op.terms = terms;
     op.dma = attach_dma(bd, p, 1, 2, bd.plan->ops) ? 1 : 0;
     if (!op.dma) { bd.ok = false; e->err = "phase upsampling conv: conv_dma refused a launch it had accepted"; return false; }
     op.cp = p; op.stride = 1; op.up = 2; op.flops = conv_flops(p);
@@ -927,11 +752,9 @@ static Tensor resample_conv(Builder& bd, const std::string& pfx, const Tensor& x
     const int H = down ? x.H / 2 : x.H * 2, Wd = down ? x.W / 2 : x.W * 2;
     Tensor out = bd.make(x.C, H, Wd, true);
     ConvParams p = base_params(B, H, Wd, x.H, x.W, out);
-    add_seg(p, x, 0, 9, 0);
     p.addvec = upload(e, pfx + "bias", W(e, pfx + "bias").data); p.addvec_bs = 0;
-    if (down || !push_conv_up_phase(bd, p, pfx + "weight")) {
-        fill_packed_seg(p.seg[0], packed_conv(e, pfx + "weight", 0, x.C), 9, x.C);
-        p.seg[0].w16 = packed_conv16(e, pfx + "weight", 0, x.C);
+    if (down || !push_conv_up_phase(bd, p, x, pfx + "weight")) {
+        packed_seg(e, p, x, 0, 9, 0, pfx + "weight", 0, x.C);
         push_conv(bd, p, down ? 2 : 1, down ? 0 : 1);
     }
     if (bd.plan->retain) {
@@ -998,22 +821,8 @@ static int unet_walk(pf_engine* e, Builder& bd, Plan* plan) {
         op.ep.bias = upload(e, "begin_conv.bias", W(e, "begin_conv.bias").data);
         op.ep.B = B; op.ep.H = H0; op.ep.W = H0; op.ep.Cimg = ci_n; op.ep.C = ch;
         op.ep.stats_out = t0.stats;              // (sum, sumsq) per channel for the first GroupNorm, reduced in the same kernel
-        if (ch == 32 && e->precision != 0 && (ci_n == 1 || ci_n == 3)) {
-            // begin_conv2_kernel's B fragments: MFMA k of (step s, half hh, j) = 16 s + 8 hh + j = input channel * 9 + tap (zero beyond 9 Cimg),
-            // column n = output channel, x 2^8 and split like every packed conv weight
-            std::vector<_Float16> wm((size_t)2 * 2 * 64 * 8, (_Float16)0.f);
-            for (int sk = 0; sk < 2; ++sk) for (int ln = 0; ln < 64; ++ln) for (int j = 0; j < 8; ++j) {
-                const int n = ln & 31, hh = ln >> 5, kk = 16 * sk + 8 * hh + j;
-                if (kk >= 9 * ci_n) continue;
-                const int ci = kk / 9, tap = kk % 9;
-                const float wv = w.data[((size_t)n * ci_n + ci) * 9 + tap] * 256.0f;
-                const _Float16 hi = (_Float16)wv, lo = (_Float16)(wv - (float)hi);
-                wm[(((size_t)sk * 2 + 0) * 64 + ln) * 8 + j] = hi; wm[(((size_t)sk * 2 + 1) * 64 + ln) * 8 + j] = lo;
-            }
-            std::vector<float> raw(wm.size() / 2);
-            memcpy(raw.data(), wm.data(), wm.size() * sizeof(_Float16));
-            op.ep.w16 = upload(e, "begin_conv.mfma16", raw);
-        }
+        if (ch == 32 && e->precision != 0 && (ci_n == 1 || ci_n == 3))      // begin_conv2_kernel's B fragments
+            op.ep.w16 = weight_image(e, "begin_conv.mfma16", [&] { return wpack::edge_frag(oihw(e, "begin_conv.weight"), true); });
         plan->ops.push_back(op);
         hs.push_back(t0);
         plan->t_begin = t0;
@@ -1077,22 +886,8 @@ static int unet_walk(pf_engine* e, Builder& bd, Plan* plan) {
         op.ep.stats = h.stats; op.ep.gamma = upload(e, "end_conv.0.weight", W(e, "end_conv.0.weight").data);
         op.ep.beta = upload(e, "end_conv.0.bias", W(e, "end_conv.0.bias").data);
         op.ep.gn_cpg = ch / 32; op.ep.gn_eps = 1e-6f;
-        if (ch == 32 && e->precision != 0) {
-            // end_conv2_kernel's B fragments: MFMA k of (step s, half hh, j) = channel 16 hh + 8 s + j, column n = tap * Cimg + co (zero beyond
-            // 9 Cimg), x 2^8 and split like every packed conv weight
-            std::vector<_Float16> wm((size_t)2 * 2 * 64 * 8, (_Float16)0.f);
-            for (int sk = 0; sk < 2; ++sk) for (int ln = 0; ln < 64; ++ln) for (int j = 0; j < 8; ++j) {
-                const int n = ln & 31, hh = ln >> 5, cc = 16 * hh + 8 * sk + j;
-                if (n >= 9 * co_n) continue;
-                const int tap = n / co_n, co = n % co_n;
-                const float wv = w.data[((size_t)co * ch + cc) * 9 + tap] * 256.0f;
-                const _Float16 hi = (_Float16)wv, lo = (_Float16)(wv - (float)hi);
-                wm[(((size_t)sk * 2 + 0) * 64 + ln) * 8 + j] = hi; wm[(((size_t)sk * 2 + 1) * 64 + ln) * 8 + j] = lo;
-            }
-            std::vector<float> raw(wm.size() / 2);
-            memcpy(raw.data(), wm.data(), wm.size() * sizeof(_Float16));
-            op.ep.w16 = upload(e, "end_conv.mfma16", raw);
-        }
+        if (ch == 32 && e->precision != 0)      // end_conv2_kernel's B fragments
+            op.ep.w16 = weight_image(e, "end_conv.mfma16", [&] { return wpack::edge_frag(oihw(e, "end_conv.2.weight"), false); });
         plan->ops.push_back(op);
         plan->t_last = h;
     }
@@ -1160,24 +955,15 @@ static int build_plan(pf_engine* e, int B, bool retain, Plan** out_plan) {
 // gradient).  Walks the forward tape in reverse; every dense step reuses conv_mfma_kernel with
 // transposed (and spatially flipped) weight repacks.
 // --------------------------------------------------------------------------------------
-// OIHW weight, input channels [lo,hi)  ->  adjoint conv weight  W'[ci][co][ky][kx] = W[co][lo+ci][K-1-ky][K-1-kx]
-static float* packed_conv_T(pf_engine* e, const std::string& wname, int lo, int hi) {
-    const std::string key = wname + "#T" + std::to_string(lo) + ":" + std::to_string(hi);
+// the adjoint conv's weight over input channels [lo, hi) (wpack::adjoint), registered as the host tensor `wname#T<lo>:<hi>` the ordinary packers read
+static std::string adjoint_weight(pf_engine* e, const std::string& wname, int lo, int hi) {
+    const std::string key = wname + "#T" + range_key(lo, hi);
     if (!e->host.count(key)) {
-        const HostTensor& t = W(e, wname);
-        const int O = (int)t.shape[0], I = (int)t.shape[1], K = (int)t.shape[2], kk = K * K, C = hi - lo;
-        HostTensor tt; tt.shape = {C, O, K, K}; tt.data.resize((size_t)C * O * kk); tt.loaded = true;
-        for (int ci = 0; ci < C; ++ci) for (int co = 0; co < O; ++co) for (int tap = 0; tap < kk; ++tap)
-            tt.data[((size_t)ci * O + co) * kk + tap] = t.data[((size_t)co * I + lo + ci) * kk + (kk - 1 - tap)];
+        const wpack::Oihw w = oihw(e, wname); const int64_t K = W(e, wname).shape[2];
+        HostTensor tt; tt.shape = {hi - lo, w.O, K, K}; tt.data = wpack::adjoint(w, lo, hi); tt.loaded = true;
         e->host[key] = std::move(tt);
     }
-    return packed_conv(e, key, 0, (int)e->host.at(key).shape[1]);
-}
-
-static const void* packed_conv16_T(pf_engine* e, const std::string& wname, int lo, int hi) {
-    packed_conv_T(e, wname, lo, hi);      // creates the transposed host tensor
-    const std::string key = wname + "#T" + std::to_string(lo) + ":" + std::to_string(hi);
-    return packed_conv16(e, key, 0, (int)e->host.at(key).shape[1]);
+    return key;
 }
 
 struct GradEntry { Tensor t; bool has = false; };
@@ -1202,12 +988,10 @@ struct BwdCtx {
         p.out = dst.t.p; p.out_cstride = dst.t.C;
         if (dst.has) { p.residual = dst.t.p; p.res_cstride = dst.t.C; }
         dst.has = true;
-        Op op{}; op.kind = OP_CONV; op.cp = p; op.stride = stride; op.up = up; op.flops = conv_flops(p);
-        plan->bwd_flops += op.flops;
-        push(op);
+        conv_plain(p, stride, up);
     }
     void conv_plain(const ConvParams& p, int stride = 1, int up = 0) {
-        Op op{}; op.kind = OP_CONV; op.cp = p; op.stride = stride; op.up = up; op.flops = conv_flops(p);
+        Op op{}; op.kind = OP_CONV; op.terms = conv_terms(e); op.cp = p; op.stride = stride; op.up = up; op.flops = conv_flops(p);
         plan->bwd_flops += op.flops;
         push(op);
     }
@@ -1222,6 +1006,12 @@ static void raw_seg(ConvParams& p, const float* src, int C, int cstride, int tap
     ConvSeg& s = p.seg[p.nseg++];
     s.src = src; s.C = C; s.cstride = cstride; s.coff = 0; s.xform = 0; s.taps = taps; s.gn_off = 0; s.stats = nullptr;
     s.w = w; s.w_mode = 0; s.w_bs = 0; s.w_cs = 0; s.w_ts = 0; s.w_ns = 0; s.w_ks = 0; s.w16 = w16;
+}
+// K-segment of an adjoint conv: the raw gradient `src` against the transposed, tap-flipped weight slice [lo, hi) of `wname`
+static void adj_seg(pf_engine* e, ConvParams& p, const float* src, int C, int cstride, int taps, const std::string& wname, int lo, int hi) {
+    const std::string key = adjoint_weight(e, wname, lo, hi);
+    const int cin = (int)W(e, key).shape[1];
+    raw_seg(p, src, C, cstride, taps, packed_conv(e, key, 0, cin), packed_conv16(e, key, 0, cin));
 }
 static void gen_seg(ConvParams& p, const float* src, int C, int cstride, const float* w, int64_t w_bs, int64_t w_ns, int64_t w_ks) {
     ConvSeg& s = p.seg[p.nseg++];
@@ -1314,7 +1104,7 @@ static void bwd_attn(BwdCtx& c, const TapeRec& tr, GradEntry& gout) {
     // d(o) = dout . Wproj
     Tensor d_o = c.tmp(C, H, Wd);
     { ConvParams p = bwd_params(B, H, Wd, H, Wd, C);
-      raw_seg(p, gout.t.p, C, C, 1, packed_conv_T(e, tr.pfx + "proj_out.weight", 0, C), packed_conv16_T(e, tr.pfx + "proj_out.weight", 0, C)); p.out = d_o.p; p.out_cstride = C;
+      adj_seg(e, p, gout.t.p, C, C, 1, tr.pfx + "proj_out.weight", 0, C); p.out = d_o.p; p.out_cstride = C;
       p.out_scale = tr.s; c.conv_plain(p); }
     // dA[i][j] = sum_c d_o[i][c] v[j][c]
     Tensor dA = c.tmp(HW, H, Wd);
@@ -1339,7 +1129,7 @@ static void bwd_attn(BwdCtx& c, const TapeRec& tr, GradEntry& gout) {
     Tensor dhn = c.tmp(C, H, Wd);
     GnBwd gna = gn_bwd_begin(c, {x}, tr.pfx + "norm.", false, tr.groups);
     { ConvParams p = bwd_params(B, H, Wd, H, Wd, C);
-      raw_seg(p, dqkv.p, 3 * C, 3 * C, 1, packed_conv_T(e, tr.pfx + "qkv.w", 0, C), packed_conv16_T(e, tr.pfx + "qkv.w", 0, C)); p.out = dhn.p; p.out_cstride = C;
+      adj_seg(e, p, dqkv.p, 3 * C, 3 * C, 1, tr.pfx + "qkv.w", 0, C); p.out = dhn.p; p.out_cstride = C;
       gn_bwd_fuse(c, gna, 0, p);
       c.conv_plain(p); }
     gn_bwd_finish(c, gna, {dhn}, {&c.G(x)}, {gout.t.p}, tr.s);
@@ -1406,7 +1196,7 @@ static int build_backward(pf_engine* e, Plan* plan, Builder& bd) {
             // out = conv(nearest_up(x)): dU = adjoint conv at the fine resolution, dx = 2x2 sum-pool of dU
             Tensor dU = c.tmp(tr.in0.C, H, Wd);
             ConvParams p = bwd_params(B, H, Wd, H, Wd, tr.in0.C);
-            raw_seg(p, gout.t.p, tr.out.C, tr.out.C, 9, packed_conv_T(e, tr.pfx + "weight", 0, tr.in0.C), packed_conv16_T(e, tr.pfx + "weight", 0, tr.in0.C));
+            adj_seg(e, p, gout.t.p, tr.out.C, tr.out.C, 9, tr.pfx + "weight", 0, tr.in0.C);
             p.out = dU.p; p.out_cstride = dU.C; c.conv_plain(p);
             GradEntry& gx = c.G(tr.in0);
             Op op{}; op.kind = OP_SUMPOOL; op.P[0] = dU.p; op.O = gx.t.p; op.I[0] = tr.in0.H; op.I[1] = tr.in0.W; op.I[2] = tr.in0.C; op.I[3] = gx.has ? 1 : 0;
@@ -1445,7 +1235,7 @@ static int build_backward(pf_engine* e, Plan* plan, Builder& bd) {
         } else if (tr.kind == TP_DOWN) {
             // out = conv_stride2(x): dx = adjoint conv of the zero-inserted gradient
             ConvParams p = bwd_params(B, tr.in0.H, tr.in0.W, H, Wd, tr.in0.C);
-            raw_seg(p, gout.t.p, tr.out.C, tr.out.C, 9, packed_conv_T(e, tr.pfx + "weight", 0, tr.in0.C), packed_conv16_T(e, tr.pfx + "weight", 0, tr.in0.C));
+            adj_seg(e, p, gout.t.p, tr.out.C, tr.out.C, 9, tr.pfx + "weight", 0, tr.in0.C);
             c.conv_to(p, c.G(tr.in0), 1, 2);
         } else if (tr.kind == TP_RES) {
             const ResDesc& r = *tr.r;
@@ -1455,7 +1245,7 @@ static int build_backward(pf_engine* e, Plan* plan, Builder& bd) {
             GnBwd gn2 = gn_bwd_begin(c, {tr.h1}, r.prefix + "norm2.", true);
             {
                 ConvParams p = bwd_params(B, H, Wd, H, Wd, r.cout);
-                raw_seg(p, gout.t.p, r.cout, r.cout, 9, packed_conv_T(e, r.prefix + "conv2.weight", 0, r.cout), packed_conv16_T(e, r.prefix + "conv2.weight", 0, r.cout));
+                adj_seg(e, p, gout.t.p, r.cout, r.cout, 9, r.prefix + "conv2.weight", 0, r.cout);
                 p.out = t1.p; p.out_cstride = r.cout;
                 gn_bwd_fuse(c, gn2, 0, p);
                 c.conv_plain(p);
@@ -1472,7 +1262,7 @@ static int build_backward(pf_engine* e, Plan* plan, Builder& bd) {
                 const Tensor& sT = srcs[sj];
                 Tensor u = c.tmp(sT.C, H, Wd);
                 ConvParams p = bwd_params(B, H, Wd, H, Wd, sT.C);
-                raw_seg(p, gh1.t.p, r.cout, r.cout, 9, packed_conv_T(e, r.prefix + "conv1.weight", lo, lo + sT.C), packed_conv16_T(e, r.prefix + "conv1.weight", lo, lo + sT.C));
+                adj_seg(e, p, gh1.t.p, r.cout, r.cout, 9, r.prefix + "conv1.weight", lo, lo + sT.C);
                 p.out = u.p; p.out_cstride = sT.C;
                 gn_bwd_fuse(c, gn1, sj, p);
                 c.conv_plain(p);
@@ -1480,7 +1270,7 @@ static int build_backward(pf_engine* e, Plan* plan, Builder& bd) {
                 GradEntry& gd = c.G(sT);
                 if (cin != r.cout) {   // 1x1 shortcut adjoint goes straight into the gradient buffer
                     ConvParams q = bwd_params(B, H, Wd, H, Wd, sT.C);
-                    raw_seg(q, gout.t.p, r.cout, r.cout, 1, packed_conv_T(e, r.prefix + "shortcut.weight", lo, lo + sT.C), packed_conv16_T(e, r.prefix + "shortcut.weight", lo, lo + sT.C));
+                    adj_seg(e, q, gout.t.p, r.cout, r.cout, 1, r.prefix + "shortcut.weight", lo, lo + sT.C);
                     c.conv_to(q, gd);
                     adds.push_back(nullptr);
                 } else {
@@ -1533,7 +1323,7 @@ static hipError_t zero_fill(void* ptr, size_t bytes, hipStream_t s) {
 
 #include "engine_ncsnpp_bwd.inc"
 
-static hipError_t dispatch_conv(pf_engine* e, const Op& op, hipStream_t s);
+static hipError_t dispatch_conv(const Op& op, hipStream_t s);
 static int run_backward(pf_engine* e, Plan* plan, const float* vec, float* g, hipStream_t s) {
     const int B = plan->B;
     // J^T is linear in vec: normalise vec by a power of two (exact) so that the split-fp16 adjoint convs stay in
@@ -1548,7 +1338,7 @@ static int run_backward(pf_engine* e, Plan* plan, const float* vec, float* g, hi
             case OP_MEMSET: if (op.bytes) r = zero_fill(op.ptr, op.bytes, s); break;
             case OP_BEGIN: { EdgeConvParams ep = op.ep; ep.in = vec; r = launch_begin_conv(ep, s); break; }
             case OP_END: { EdgeConvParams ep = op.ep; ep.out = g; r = launch_end_conv(ep, s); break; }
-            case OP_CONV: r = dispatch_conv(e, op, s); break;
+            case OP_CONV: r = dispatch_conv(op, s); break;
             case OP_PREP: r = launch_prep_split(op.pp, s); break;
             case OP_GN_FWD_COEF:
                 r = launch_gn_fwd_coeffs((const double*)op.P[0], op.I[0], (const double*)op.P[1], op.I[1], op.I[2], op.I[3], 1e-6f, (float*)op.P[2],
@@ -1576,14 +1366,14 @@ static int run_backward(pf_engine* e, Plan* plan, const float* vec, float* g, hi
     return PF_OK;
 }
 
-static hipError_t dispatch_conv(pf_engine* e, const Op& op, hipStream_t s) {
-    if (op.use_pp == 2 && e->precision != 0) return launch_conv_sp(op.ppp, s, e->precision == 2 ? 1 : 3);
-    if (op.use_pp == 1 && e->precision != 0) return launch_conv_pp(op.ppp, s, e->precision == 2 ? 1 : 3);
-    if (op.dma) return launch_conv_dma(op.cp, op.up, s, e->precision == 2 ? 1 : 3);
-    if (e->precision != 0) {
+static hipError_t dispatch_conv(const Op& op, hipStream_t s) {
+    if (op.use_pp == 2) return launch_conv_sp(op.ppp, s, op.terms);
+    if (op.use_pp == 1) return launch_conv_pp(op.ppp, s, op.terms);
+    if (op.dma) return launch_conv_dma(op.cp, op.up, s, op.terms);
+    if (op.terms != 0) {
         bool ok16 = true;
         for (int i = 0; i < op.cp.nseg; ++i) ok16 &= op.cp.seg[i].w_mode == 0 && op.cp.seg[i].w16 != nullptr;
-        if (ok16) return launch_conv16(op.cp, op.stride, op.up, s, e->precision == 2 ? 1 : 3);
+        if (ok16) return launch_conv16(op.cp, op.stride, op.up, s, op.terms);
     }
     return launch_conv(op.cp, op.stride, op.up, s);
 }
@@ -1617,11 +1407,11 @@ static int run_plan(pf_engine* e, Plan* plan, const float* x, const float* t, fl
                     e->ev_ops[e->ev_used - 1] = &op;
                     if (!prep_open) hipEventRecord(ev.first, s);
                     prep_open = false;
-                    r = dispatch_conv(e, op, s);
+                    r = dispatch_conv(op, s);
                     hipEventRecord(ev.second, s);
                     e->prof_flops += (double)op.flops;
                 } else {
-                    r = dispatch_conv(e, op, s);
+                    r = dispatch_conv(op, s);
                 }
                 break;
             case OP_SOFTMAX: r = launch_softmax_rows(op.sm, op.sm_rows, op.sm_cols, s); break;

@@ -114,12 +114,6 @@ static void nx_alias_attn(pf_engine* e, int idx) {
     e->host[P + "norm.bias"] = W(e, P + "GroupNorm_0.bias");
 }
 
-static void nx_packed_seg(pf_engine* e, ConvParams& p, const Tensor& t, int xform, int taps, int gn_off, const std::string& wname, int lo, int hi) {
-    add_seg(p, t, xform, taps, gn_off);
-    fill_packed_seg(p.seg[p.nseg - 1], packed_conv(e, wname, lo, hi), taps, p.Cout);
-    p.seg[p.nseg - 1].w16 = packed_conv16(e, wname, lo, hi);
-}
-
 static void nx_fir_kernel(const pf_ncsnpp_cfg& c, bool up, FirParams& f) {
     // _setup_kernel (up_or_down_sampling.py:191-199): outer product, / sum, in fp32; upsampling gains factor^2 (:231)
     const int K = c.fir_taps;
@@ -176,10 +170,10 @@ static Tensor nx_res_block(Builder& bd, int idx, const Tensor& in0, const Tensor
     {
         ConvParams p = base_params(B, H, Wd, H, Wd, h1);
         if (resample) {
-            nx_packed_seg(e, p, hact, 0, 9, 0, P + "Conv_0.weight", 0, in0.C);
+            packed_seg(e, p, hact, 0, 9, 0, P + "Conv_0.weight", 0, in0.C);
         } else {
-            nx_packed_seg(e, p, in0, 2, 9, 0, P + "Conv_0.weight", 0, in0.C);
-            if (in1) nx_packed_seg(e, p, *in1, 2, 9, in0.C, P + "Conv_0.weight", in0.C, cin);
+            packed_seg(e, p, in0, 2, 9, 0, P + "Conv_0.weight", 0, in0.C);
+            if (in1) packed_seg(e, p, *in1, 2, 9, in0.C, P + "Conv_0.weight", in0.C, cin);
             p.gn_C = cin; p.gn_cpg = cin / nx_groups(cin);
             p.gamma = upload(e, P + "GroupNorm_0.weight", W(e, P + "GroupNorm_0.weight").data);
             p.beta = upload(e, P + "GroupNorm_0.bias", W(e, P + "GroupNorm_0.bias").data);
@@ -192,15 +186,15 @@ static Tensor nx_res_block(Builder& bd, int idx, const Tensor& in0, const Tensor
     Tensor out = bd.make(cout, H, Wd, true);
     {
         ConvParams p = base_params(B, H, Wd, H, Wd, out);
-        nx_packed_seg(e, p, h1, 2, 9, 0, P + "Conv_1.weight", 0, cout);
+        packed_seg(e, p, h1, 2, 9, 0, P + "Conv_1.weight", 0, cout);
         p.gn_C = cout; p.gn_cpg = cout / nx_groups(cout);
         p.gamma = upload(e, P + "GroupNorm_1.weight", W(e, P + "GroupNorm_1.weight").data);
         p.beta = upload(e, P + "GroupNorm_1.bias", W(e, P + "GroupNorm_1.bias").data);
         std::vector<float> bias = W(e, P + "Conv_1.bias").data;
         if (cin != cout || resample) {
             const Tensor& x0 = resample ? xres : in0;
-            nx_packed_seg(e, p, x0, 0, 1, 0, P + "Conv_2.weight", 0, in0.C);
-            if (in1) nx_packed_seg(e, p, *in1, 0, 1, 0, P + "Conv_2.weight", in0.C, cin);
+            packed_seg(e, p, x0, 0, 1, 0, P + "Conv_2.weight", 0, in0.C);
+            if (in1) packed_seg(e, p, *in1, 0, 1, 0, P + "Conv_2.weight", in0.C, cin);
             const auto& sb = W(e, P + "Conv_2.bias").data;
             for (size_t i = 0; i < bias.size(); ++i) bias[i] += sb[i];
         } else {
@@ -219,7 +213,7 @@ static Tensor nx_res_block(Builder& bd, int idx, const Tensor& in0, const Tensor
                 for (int o = 0; o < O; ++o) for (int i = 0; i < I; ++i) d[(size_t)o * 32 + i] = w.data[(size_t)o * I + i] * inv;
             });
             if (p.nseg >= 3) { e->err = "internal: too many K-segments"; bd.ok = false; return out; }
-            nx_packed_seg(e, p, *pyr, 0, 1, 0, key, 0, 32);
+            packed_seg(e, p, *pyr, 0, 1, 0, key, 0, 32);
             const auto& cb = W(e, nx_name(idx + 1, "Conv_0.bias")).data;
             for (size_t i = 0; i < bias.size(); ++i) bias[i] += cb[i];
         }
@@ -278,7 +272,7 @@ static int nx_walk(pf_engine* e, Builder& bd, Plan* plan) {
         });
         Tensor t0 = bd.make(nf, H0, H0, true);
         ConvParams p = base_params(B, H0, H0, H0, H0, t0);
-        nx_packed_seg(e, p, pyr_in, 0, 9, 0, key, 0, 32);
+        packed_seg(e, p, pyr_in, 0, 9, 0, key, 0, 32);
         p.addvec = upload(e, nx_name(m_idx, "bias"), W(e, nx_name(m_idx, "bias")).data); p.addvec_bs = 0;
         push_conv(bd, p);
         hs.push_back(t0); plan->taps.push_back({"conv_in", t0});
@@ -346,7 +340,7 @@ static int nx_walk(pf_engine* e, Builder& bd, Plan* plan) {
             { const auto& bb = W(e, nx_name(ci, "bias")).data; std::copy(bb.begin(), bb.end(), b32.begin()); }
             Tensor np = bd.make(32, h.H, h.W, false);
             ConvParams p = base_params(B, h.H, h.W, h.H, h.W, np);
-            nx_packed_seg(e, p, h, 2, 9, 0, key, 0, I);
+            packed_seg(e, p, h, 2, 9, 0, key, 0, I);
             p.gn_C = h.C; p.gn_cpg = h.C / nx_groups(h.C);
             p.gamma = upload(e, nx_name(gi, "weight"), W(e, nx_name(gi, "weight")).data);
             p.beta = upload(e, nx_name(gi, "bias"), W(e, nx_name(gi, "bias")).data);

@@ -50,7 +50,7 @@ static int nx_build_backward(pf_engine* e, Plan* plan, Builder& bd) {
             Tensor da = c.tmp(C, H, Wd);
             GnBwd g = gn_bwd_begin(c, {tr.in0}, nx_name(gi, ""), true, nx_groups(C));
             ConvParams p = bwd_params(B, H, Wd, H, Wd, C);
-            raw_seg(p, gout.t.p, 32, 32, 9, packed_conv_T(e, key, 0, C), packed_conv16_T(e, key, 0, C));
+            adj_seg(e, p, gout.t.p, 32, 32, 9, key, 0, C);
             p.out = da.p; p.out_cstride = C;
             gn_bwd_fuse(c, g, 0, p);
             c.conv_plain(p);
@@ -69,7 +69,7 @@ static int nx_build_backward(pf_engine* e, Plan* plan, Builder& bd) {
             const std::string key = nx_name(tr.idx, "weight") + "#pad32";
             const int nf = tr.out.C;
             ConvParams p = bwd_params(B, H, Wd, H, Wd, 32);
-            raw_seg(p, gout.t.p, nf, nf, 9, packed_conv_T(e, key, 0, 32), packed_conv16_T(e, key, 0, 32));
+            adj_seg(e, p, gout.t.p, nf, nf, 9, key, 0, 32);
             c.conv_to(p, c.G(tr.in0));
         } else if (tr.kind == TP_NX_RES) {
             const NxMod& m = e->nx_mods[tr.idx];
@@ -81,7 +81,7 @@ static int nx_build_backward(pf_engine* e, Plan* plan, Builder& bd) {
             GnBwd gn1 = gn_bwd_begin(c, {tr.h1}, P + "GroupNorm_1.", true, nx_groups(cout));
             {
                 ConvParams p = bwd_params(B, H, Wd, H, Wd, cout);
-                raw_seg(p, gout.t.p, cout, cout, 9, packed_conv_T(e, P + "Conv_1.weight", 0, cout), packed_conv16_T(e, P + "Conv_1.weight", 0, cout));
+                adj_seg(e, p, gout.t.p, cout, cout, 9, P + "Conv_1.weight", 0, cout);
                 p.out = t1.p; p.out_cstride = cout; p.out_scale = s;
                 gn_bwd_fuse(c, gn1, 0, p);
                 c.conv_plain(p);
@@ -97,7 +97,7 @@ static int nx_build_backward(pf_engine* e, Plan* plan, Builder& bd) {
                     for (int o = 0; o < O; ++o) for (int i = 0; i < I; ++i) d[(size_t)o * 32 + i] = w.data[(size_t)o * I + i];
                 });
                 ConvParams p = bwd_params(B, H, Wd, H, Wd, 32);
-                raw_seg(p, gout.t.p, cout, cout, 1, packed_conv_T(e, key, 0, 32), packed_conv16_T(e, key, 0, 32));
+                adj_seg(e, p, gout.t.p, cout, cout, 1, key, 0, 32);
                 c.conv_to(p, c.G(tr.pyr));
             }
             if (!tr.resample) {
@@ -109,7 +109,7 @@ static int nx_build_backward(pf_engine* e, Plan* plan, Builder& bd) {
                     const Tensor& sT = srcs[sj];
                     Tensor u = c.tmp(sT.C, H, Wd);
                     ConvParams p = bwd_params(B, H, Wd, H, Wd, sT.C);
-                    raw_seg(p, gh1.t.p, cout, cout, 9, packed_conv_T(e, P + "Conv_0.weight", lo, lo + sT.C), packed_conv16_T(e, P + "Conv_0.weight", lo, lo + sT.C));
+                    adj_seg(e, p, gh1.t.p, cout, cout, 9, P + "Conv_0.weight", lo, lo + sT.C);
                     p.out = u.p; p.out_cstride = sT.C;
                     gn_bwd_fuse(c, gn0, sj, p);
                     c.conv_plain(p);
@@ -117,7 +117,7 @@ static int nx_build_backward(pf_engine* e, Plan* plan, Builder& bd) {
                     GradEntry& gd = c.G(sT);
                     if (cin != cout) {       // s * Conv_2^T(gout) straight into the gradient buffer
                         ConvParams q = bwd_params(B, H, Wd, H, Wd, sT.C);
-                        raw_seg(q, gout.t.p, cout, cout, 1, packed_conv_T(e, P + "Conv_2.weight", lo, lo + sT.C), packed_conv16_T(e, P + "Conv_2.weight", lo, lo + sT.C));
+                        adj_seg(e, q, gout.t.p, cout, cout, 1, P + "Conv_2.weight", lo, lo + sT.C);
                         q.out_scale = s;
                         c.conv_to(q, gd);
                         adds.push_back(nullptr);
@@ -135,7 +135,7 @@ static int nx_build_backward(pf_engine* e, Plan* plan, Builder& bd) {
                 Tensor dh = c.tmp(x.C, H, Wd);
                 {
                     ConvParams p = bwd_params(B, H, Wd, H, Wd, x.C);
-                    raw_seg(p, gh1.t.p, cout, cout, 9, packed_conv_T(e, P + "Conv_0.weight", 0, x.C), packed_conv16_T(e, P + "Conv_0.weight", 0, x.C));
+                    adj_seg(e, p, gh1.t.p, cout, cout, 9, P + "Conv_0.weight", 0, x.C);
                     p.out = dh.p; p.out_cstride = x.C; c.conv_plain(p);
                 }
                 Tensor da = c.tmp(x.C, x.H, x.W);
@@ -143,7 +143,7 @@ static int nx_build_backward(pf_engine* e, Plan* plan, Builder& bd) {
                 Tensor dxr = c.tmp(x.C, H, Wd);
                 {
                     ConvParams q = bwd_params(B, H, Wd, H, Wd, x.C);
-                    raw_seg(q, gout.t.p, cout, cout, 1, packed_conv_T(e, P + "Conv_2.weight", 0, x.C), packed_conv16_T(e, P + "Conv_2.weight", 0, x.C));
+                    adj_seg(e, q, gout.t.p, cout, cout, 1, P + "Conv_2.weight", 0, x.C);
                     q.out = dxr.p; q.out_cstride = x.C; q.out_scale = s; c.conv_plain(q);
                 }
                 Tensor tx = c.tmp(x.C, x.H, x.W);

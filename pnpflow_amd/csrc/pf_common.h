@@ -46,11 +46,11 @@ struct ConvSeg {
     int gn_off;           // index of this segment's channel 0 in the GroupNorm channel space
     const double* stats;  // [B][C][2] per-channel (sum, sumsq) of src, or nullptr
     const float* w;       // weights
-    int w_mode;           // 0: fragment-major repack [chunk][tap][kstep(2)][Cout][8] (see packed_conv)
+    int w_mode;           // 0: fragment-major fp32 repack (wpack::frag32, weight_pack.h)
                           // 1: generic strided operand: element (n,k) at b*w_bs + n*w_ns + k*w_ks
     int64_t w_bs, w_cs, w_ts, w_ns, w_ks;
-    const void* w16;      // optional split-fp16 repack [chunk][tap][Cout][16 hi | 16 lo] (x256), see conv_mfma16.hip
-    const void* w16h;     // optional hi-only repack [slice16][tap][Cout][16 hi] (x256) of the single-term mode's LDS-DMA kernel (conv_dma.hip)
+    const void* w16;      // optional split-fp16 repack of the same slice (x 2^8): wpack::slice16 at terms 3 (weight_pack.h), read by conv_mfma16.hip / conv_dma.hip
+    const void* w16h;     // optional hi-only repack (wpack::slice16 at terms 1) of the single-term mode's LDS-DMA kernel (conv_dma.hip)
     const void* a16;      // conv_dma.hip only: the pre-transformed fp16 operand of this segment (prep_split_kernel), or nullptr
     int oy, ox;           // conv_mfma16.hip, taps == 4 only: the segment's 2 x 2 window covers patch rows oy + {0, 1}, columns ox + {0, 1} of the 3 x 3 neighbourhood
 };
@@ -134,7 +134,7 @@ struct EdgeConvParams {
     // end conv only: GroupNorm+SiLU of the input
     const double* stats; const float* gamma; const float* beta; int gn_cpg; float gn_eps;
     double* stats_out;    // begin conv: per-channel stats of the output
-    const void* w16;      // split-fp16 MFMA weight image [k-step 2][hi | lo][lane 64][8 halfs], x 2^8 (engine.hip): end conv in its GroupNorm + SiLU form (k = channel), begin conv forward (k = input channel * 9 + tap); nullptr: the VALU kernels
+    const void* w16;      // split-fp16 MFMA weight image [k-step 2][hi | lo][lane 64][8 halfs], x 2^8 (wpack::edge_frag, weight_pack.h): end conv in its GroupNorm + SiLU form (k = channel), begin conv forward (k = input channel * 9 + tap); nullptr: the VALU kernels
 };
 
 // fused attention core (attention.hip): qkv [B][T][3C] (q | k | v) -> out [B][T][C]
@@ -193,7 +193,7 @@ size_t conv_dma_a16_bytes(int B, int C, int Hs, int Ws, int terms);
 
 // conv_pp.hip: persistent two-team kernel of the full-resolution 32-channel level.  A launch is a list of 32-channel K-chunks (9-tap chunks
 // with GroupNorm(+SiLU) staging first, then raw 1-tap chunks of a folded 1x1 shortcut), each with its own LDS weight image
-// [k16-step = tap * 2 + j][hi | lo][k-half][Cout = 32][8 halfs] (values x 2^8, split like packed_conv16).
+// (layouts in weight_pack.h: wpack::chunk_pp; wpack::chunk_sp for the 16-channel chunks of conv_sp.hip).
 constexpr int PP_MAXCH = 24;     // conv_pp: <= 4 chunks of 32 channels; conv_sp: <= 24 chunks of 16 channels (cat[256, 128] -> 128)
 struct PPChunk {
     const float* src;     // NHWC source tensor of the chunk's K-segment

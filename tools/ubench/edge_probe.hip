@@ -2,6 +2,7 @@
 // tensors - outputs compared, launches timed - begin_conv_kernel timed, and the chip's pure float4 write / read streaming times of the same tensor.
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../../pnpflow_amd/csrc -o edge_probe edge_probe.hip      run: ./edge_probe [H W B Cimg]
 #include "../../pnpflow_amd/csrc/unet_misc.hip"
+#include "../../pnpflow_amd/csrc/weight_pack.h"
 #include <cstdio>
 #include <cmath>
 #include <vector>
@@ -37,20 +38,15 @@ int main(int argc, char** argv) {
     unsigned st = 12345u;
     std::vector<float> himg(npix * CI), hact(npix * C), hwb((size_t)9 * CI * C), hbias(C), hwe((size_t)9 * CI * C), hbe(4), hg(C), hbt(C);
     for (auto& v : himg) v = frand(st); for (auto& v : hact) v = 3.f * frand(st) + 0.5f;
-    for (auto& v : hwb) v = 0.2f * frand(st); for (auto& v : hbias) v = 0.1f * frand(st);
+    // begin conv weights in the reference's layout [ch][Cimg][3][3]; VALU form [tap][ci][ch]
+    std::vector<float> wbeg((size_t)C * CI * 9); for (auto& v : wbeg) v = 0.2f * frand(st);
+    for (int n = 0; n < C; ++n) for (int ci = 0; ci < CI; ++ci) for (int tap = 0; tap < 9; ++tap) hwb[((size_t)tap * CI + ci) * C + n] = wbeg[((size_t)n * CI + ci) * 9 + tap];
+    for (auto& v : hbias) v = 0.1f * frand(st);
     for (auto& v : hbe) v = 0.1f * frand(st); for (auto& v : hg) v = 1.f + 0.3f * frand(st); for (auto& v : hbt) v = 0.2f * frand(st);
-    // end conv weights in the reference's layout [Cimg][ch][3][3], repacked as engine.hip does: VALU form [tap][co][ch], MFMA image
+    // end conv weights in the reference's layout [Cimg][ch][3][3], repacked as engine.hip does: VALU form [tap][co][ch], MFMA image (weight_pack.h)
     std::vector<float> wend((size_t)CI * C * 9); for (auto& v : wend) v = 0.1f * frand(st);
     for (int co = 0; co < CI; ++co) for (int ci = 0; ci < C; ++ci) for (int tap = 0; tap < 9; ++tap) hwe[((size_t)tap * CI + co) * C + ci] = wend[((size_t)co * C + ci) * 9 + tap];
-    std::vector<_Float16> wm((size_t)2 * 2 * 64 * 8, (_Float16)0.f);
-    for (int sk = 0; sk < 2; ++sk) for (int ln = 0; ln < 64; ++ln) for (int j = 0; j < 8; ++j) {
-        const int n = ln & 31, hh = ln >> 5, cc = 16 * hh + 8 * sk + j;
-        if (n >= 9 * CI) continue;
-        const int tap = n / CI, co = n % CI;
-        const float wv = wend[((size_t)co * C + cc) * 9 + tap] * 256.0f;
-        const _Float16 hi = (_Float16)wv, lo = (_Float16)(wv - (float)hi);
-        wm[(((size_t)sk * 2 + 0) * 64 + ln) * 8 + j] = hi; wm[(((size_t)sk * 2 + 1) * 64 + ln) * 8 + j] = lo;
-    }
+    const std::vector<_Float16> wm = wpack::edge_frag({wend.data(), CI, C, 9}, false);
     float *img, *act, *act2, *wb, *bias, *we, *be, *g, *bt, *o1, *o2; double *st1, *st2; void* w16;
     (void)hipMalloc(&img, himg.size() * 4); (void)hipMalloc(&act, hact.size() * 4); (void)hipMalloc(&act2, hact.size() * 4);
     (void)hipMalloc(&wb, hwb.size() * 4); (void)hipMalloc(&bias, 128); (void)hipMalloc(&we, hwe.size() * 4); (void)hipMalloc(&be, 16);
@@ -62,15 +58,7 @@ int main(int argc, char** argv) {
     (void)hipMemcpy(w16, wm.data(), wm.size() * 2, hipMemcpyHostToDevice);
 
     // ---- begin conv: round-1 VALU kernel against begin_conv2_kernel (MFMA) ---------------------------------------------------------------
-    std::vector<_Float16> wmb((size_t)2 * 2 * 64 * 8, (_Float16)0.f);      // engine.hip's packing: k = ci * 9 + tap, weights [tap][ci][C] in hwb
-    for (int sk = 0; sk < 2; ++sk) for (int ln = 0; ln < 64; ++ln) for (int j = 0; j < 8; ++j) {
-        const int n = ln & 31, hh = ln >> 5, kk = 16 * sk + 8 * hh + j;
-        if (kk >= 9 * CI) continue;
-        const int ci = kk / 9, tap = kk % 9;
-        const float wv = hwb[((size_t)tap * CI + ci) * C + n] * 256.0f;
-        const _Float16 hi = (_Float16)wv, lo = (_Float16)(wv - (float)hi);
-        wmb[(((size_t)sk * 2 + 0) * 64 + ln) * 8 + j] = hi; wmb[(((size_t)sk * 2 + 1) * 64 + ln) * 8 + j] = lo;
-    }
+    const std::vector<_Float16> wmb = wpack::edge_frag({wbeg.data(), C, CI, 9}, true);
     void* w16b; (void)hipMalloc(&w16b, wmb.size() * 2); (void)hipMemcpy(w16b, wmb.data(), wmb.size() * 2, hipMemcpyHostToDevice);
     EdgeConvParams p{}; p.in = img; p.w = wb; p.bias = bias; p.B = B; p.H = H; p.W = W; p.Cimg = CI; p.C = C;
     auto old_begin = [&](float* out, double* stats) { EdgeConvParams q = p; q.out = out; q.stats_out = stats; q.w16 = nullptr; (void)launch_begin_conv(q, 0); };
