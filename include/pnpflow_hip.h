@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PF_ABI_VERSION 4
+#define PF_ABI_VERSION 5
 
 typedef enum pf_status {
     PF_OK = 0,
@@ -332,6 +332,46 @@ typedef void (*pf_iter_callback)(int iteration, void* user);
 int pf_pnp_flow_restore(pf_engine* e, const pf_degradation* d, const pf_pnp_params* prm,
                         const float* y, float* x_out, int B, void* stream,
                         pf_iter_callback iter_cb, void* user);
+
+/* ---- Prox-PnP with the gradient-step denoiser (pnpflow/methods/pnp_gs.py, pnpflow/train_denoiser.py) ---------------------------
+ * The denoiser net is the same U-Net as the OT net (pnpflow/utils.py:170-180); the noise level sigma[B] is fed where the flow net takes t[B].
+ *
+ * GRADIENT_STEP_DENOISER.calculate_grad (train_denoiser.py:39-57):
+ *   N = UNet(x, sigma),  Dg = (x - N) - J_N(x)^T (x - N),  g = 0.5 sum (x - N)^2 over the whole batch
+ * sigma: device [B]; Dg, N: [B,C,H,W] (N may be NULL); g: device double[1] (may be NULL).  One retained forward and one backward;
+ * afterwards the retained forward (pf_unet_backward) is that of (x, sigma). */
+int pf_gs_denoiser_grad(pf_engine* e, const float* x, const float* sigma, float* Dg, float* N, double* g, int B, void* stream);
+
+/* Iterations [first, stop) of PROX_PNP.solve_ip's loop (pnp_gs.py:132-222) for one batch, on the device:
+ *   algo 0 (pgd, :202-222)                        z = x - lr grad_datafit(x) (skipped when skip_grad_step);  x = z - alpha Dg(z, level)
+ *   algo 1 (hqs, random_inpainting, :138-156)     Dx = x - Dg(x, level);  x = H(y) - H(Dx) + Dx on every iteration but max_iter - 1, which
+ *                                                 leaves x unchanged (its denoiser evaluation is skipped)
+ *   algo 2 (hqs, gaussian_deblurring_FFT, :158-178)  y' = 0.1 alpha (x - Dg) + alpha (1 - 0.1 alpha) x;
+ *                                                 x_new = real(ifft2(fft2(alpha H_adj(y) + y') / (alpha |fft2 filter|^2 + 1)));
+ *                                                 alpha *= 0.9 when 0.5 |H(x_new) - y|^2 - 0.5 |H(x) - y|^2 < 0.1 / alpha |x_new - x|^2
+ *                                                 (norms over the whole batch tensor)
+ * The denoiser level of iteration i is host_sigma_den[i]; alpha lives in a device double (a decay needs no host round-trip).  One
+ * iteration (retained forward, seed, hand-written backward, combine and, for algo 2, the Fourier prox, the reductions and the decision) is
+ * captured once into a hipGraph and replayed while the plan, the operator, B, algo and the coefficients stay the same.  Reductions are
+ * deterministic (fp64 per-block partials, fixed-order finish).  x_inout: the initialisation (or the iterate entering iteration `first`)
+ * on entry, the iterate after iteration stop - 1 on exit.  host_alpha_out (host double[1], may be NULL): alpha after the call.
+ * host_log (host double[2 * max_iter], may be NULL; algo 2): (gap, threshold) of every iteration run.  Afterwards the retained forward
+ * is that of the last iteration's denoiser input.  Synchronises `stream` and checks the numeric health before returning.
+ * PF_ERR_INVALID (no kernel launched): algo 1 without a PF_DEG_MASK_INPAINTING mask, algo 2 without PF_DEG_GAUSSIAN_BLUR, laplace with
+ * algo != 0, first > stop or stop > max_iter. */
+typedef struct pf_pnp_gs_params {
+    int32_t algo;                 /* 0 pgd | 1 hqs random_inpainting | 2 hqs gaussian_deblurring_FFT */
+    int32_t noise_model;          /* 0 gaussian | 1 laplace (pgd only) */
+    int32_t max_iter, first, stop;
+    int32_t skip_grad_step;       /* pgd, gaussian denoising (pnp_gs.py:204-210) */
+    const float* host_sigma_den;  /* host [max_iter]: denoiser level of each iteration */
+    float grad_coef;              /* lr / sigma^2 (gaussian) or lr / sigma (laplace) */
+    int32_t use_graph;
+    double alpha;                 /* on entry */
+    const uint8_t* host_cb_mask;  /* as pf_pnp_params */
+} pf_pnp_gs_params;
+int pf_pnp_gs_restore(pf_engine* e, const pf_degradation* d, const pf_pnp_gs_params* prm, const float* y, float* x_inout, double* host_alpha_out,
+                      double* host_log, int B, void* stream, pf_iter_callback iter_cb, void* user);
 
 /* Numeric health of the forwards run so far: every GroupNorm finalisation checks the activation statistics it consumes; an
  * overflow / NaN anywhere upstream makes them non-finite and sets a device flag.  This call synchronises `stream`, returns

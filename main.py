@@ -79,6 +79,8 @@ class SyntheticLoader:
 
 def main():
     args = parse_args()
+    if args.method == 'pnp_gs' and args.model != 'gradient_step':
+        raise SystemExit(f"method pnp_gs needs `model gradient_step` (the gradient-step denoiser), not model {args.model!r}")
     from pnpflow_amd import parallel
     rank, world, local = parallel.init_from_env()
     device = torch.device("cuda", local) if torch.cuda.is_available() else torch.device("cpu")
@@ -135,6 +137,10 @@ def main():
         elif args.method == 'd_flow':
             from pnpflow_amd.methods.d_flow import D_FLOW
             method = D_FLOW(model, device, args)
+        elif args.method == 'pnp_gs':
+            from pnpflow_amd.methods.pnp_gs import PROX_PNP
+            from pnpflow_amd.train_denoiser import GRADIENT_STEP_DENOISER
+            method = PROX_PNP(GRADIENT_STEP_DENOISER(model, device, args), device, args)
         else:
             raise ValueError("The method your entered does not exist")
         method.run_method(loaders, degradation, sigma_noise)

@@ -128,6 +128,7 @@ struct NxMod {                 // one entry of NCSNpp.all_modules (ncsnpp.py:72-
 };
 
 struct DFlowState;                 // D-Flow / dopri5 buffers and graphs (engine_dflow.inc)
+struct PnpGsState;                 // Prox-PnP (gradient-step denoiser) buffers and graph (engine_pnp_gs.inc)
 
 struct pf_engine {
     int device = 0;
@@ -174,6 +175,8 @@ struct pf_engine {
     hipStream_t work_stream = nullptr;   // used when the caller passes the NULL stream and asks for graph replay
     DFlowState* dflow = nullptr;         // pf_d_flow_* / pf_flow_ode_dopri5 state (engine_dflow.inc)
     const void* held_plans[3] = {};      // plans a cached D-Flow graph replays (kept out of the plan cache's eviction)
+    PnpGsState* pnpgs = nullptr;         // pf_gs_denoiser_grad / pf_pnp_gs_restore state (engine_pnp_gs.inc)
+    const void* held_pnpgs_plan = nullptr;   // the plan its cached graph replays (kept out of the eviction as well)
     // profiling
     bool profile = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
@@ -907,6 +910,7 @@ static int build_plan(pf_engine* e, int B, bool retain, Plan** out_plan) {
         for (auto jt = e->plans.begin(); jt != e->plans.end(); ++jt) {
             if (jt->second.get() == e->retained_plan || jt->second.get() == e->gkey.plan || jt->second.get() == e->okey.plan) continue;
             if (jt->second.get() == e->held_plans[0] || jt->second.get() == e->held_plans[1] || jt->second.get() == e->held_plans[2]) continue;
+            if (jt->second.get() == e->held_pnpgs_plan) continue;
             if (victim == e->plans.end() || jt->second->last_used < victim->second->last_used) victim = jt;
         }
         if (victim == e->plans.end()) break;
@@ -1505,9 +1509,11 @@ static void drop_graph(pf_engine* e);
 static void drop_ode_graph(pf_engine* e);
 static void drop_dflow_graphs(pf_engine* e);
 static void free_dflow(pf_engine* e);
+static void drop_pnpgs_graph(pf_engine* e);
+static void free_pnpgs(pf_engine* e);
 int pf_engine_set_solver_time_scale(pf_engine* e, float scale) {
     if (!e || !(scale > 0.f)) return PF_ERR_INVALID;
-    if (scale != e->solver_time_scale) { drop_graph(e); drop_ode_graph(e); drop_dflow_graphs(e); e->solver_time_scale = scale; }   // the captured graphs bake the scale in
+    if (scale != e->solver_time_scale) { drop_graph(e); drop_ode_graph(e); drop_dflow_graphs(e); drop_pnpgs_graph(e); e->solver_time_scale = scale; }   // the captured graphs bake the scale in
     return PF_OK;
 }
 
@@ -1560,6 +1566,7 @@ void pf_engine_destroy(pf_engine* e) {
     drop_graph(e);
     free_ode(e);
     free_dflow(e);
+    free_pnpgs(e);
     for (auto& kv : e->plans) for (void* p : kv.second->allocs) hipFree(p);
     for (void* p : e->weight_allocs) hipFree(p);
     for (auto& ev : e->ev_pool) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
@@ -1614,7 +1621,7 @@ int pf_engine_finalize_weights(pf_engine* e) {
 int pf_engine_set_precision(pf_engine* e, int mode) {
     if (!e) return PF_ERR_INVALID;
     if (mode < 0 || mode > 2) { e->err = "precision mode must be 0 (fp32 MFMA), 1 (split-fp16 MFMA, fp32-equivalent) or 2 (single fp16 MFMA)"; return PF_ERR_INVALID; }
-    if (mode != e->precision) { drop_graph(e); drop_ode_graph(e); drop_dflow_graphs(e); }       // captured graphs bake the kernel choice in
+    if (mode != e->precision) { drop_graph(e); drop_ode_graph(e); drop_dflow_graphs(e); drop_pnpgs_graph(e); }       // captured graphs bake the kernel choice in
     e->precision = mode;
     return PF_OK;
 }
@@ -2098,3 +2105,4 @@ int pf_engine_profile_read(pf_engine* e, int64_t* launches, double* ms_conv_gemm
 }  // extern "C"
 
 #include "engine_dflow.inc"
+#include "engine_pnp_gs.inc"

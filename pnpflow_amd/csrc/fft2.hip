@@ -66,7 +66,7 @@ __device__ float2* fft_lines(float2* a, float2* b, const float2* tw, int N, int 
     return b;
 }
 
-// rows forward: z[plane][row][:] = FFT_W( y - hx )
+// rows forward: z[plane][row][:] = FFT_W( y - hx )   (hx == nullptr: FFT_W( y ))
 __global__ __launch_bounds__(256) void fft_rows_fwd_kernel(const float* y, const float* hx, float2* z, int H, int W, int log2w, int LB) {
     extern __shared__ float2 smem[];
     float2* a = smem; float2* b = a + LB * W; float2* tw = b + LB * W;
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void fft_rows_fwd_kernel(const float* y, const
     for (int idx = threadIdx.x; idx < LB * W; idx += 256) {
         const int l = idx / W, k = idx - l * W;
         float v = 0.f;
-        if (row0 + l < H) { const size_t o = plane + (size_t)(row0 + l) * W + k; v = y[o] - hx[o]; }
+        if (row0 + l < H) { const size_t o = plane + (size_t)(row0 + l) * W + k; v = hx ? y[o] - hx[o] : y[o]; }
         a[idx] = make_float2(v, 0.f);
     }
     __syncthreads();
@@ -88,13 +88,15 @@ __global__ __launch_bounds__(256) void fft_rows_fwd_kernel(const float* y, const
 }
 
 // columns: forward FFT_H, divide by (rt2 * P_H[u] * P_W[v] + sigma2), inverse FFT_H - in place
-__global__ __launch_bounds__(256) void fft_cols_solve_kernel(float2* z, const float* pw_h, const float* pw_w, const float* rt2, float sigma2,
-                                                             int C, int H, int W, int log2h, int LB) {
+// alpha_dev != nullptr: the factor is the device scalar *alpha_dev for every image instead of rt2[image] (Prox-PnP's hqs deblurring prox,
+// pnp_gs.py:42: alpha |fft2 filter|^2 + 1 with sigma2 = 1)
+__global__ __launch_bounds__(256) void fft_cols_solve_kernel(float2* z, const float* pw_h, const float* pw_w, const float* rt2, const double* alpha_dev,
+                                                             float sigma2, int C, int H, int W, int log2h, int LB) {
     extern __shared__ float2 smem[];
     float2* a = smem; float2* b = a + LB * H; float2* tw = b + LB * H;
     fill_twiddles(tw, H);
     const size_t plane = (size_t)blockIdx.y * H * W;
-    const float r2 = rt2[blockIdx.y / C];
+    const float r2 = alpha_dev ? (float)*alpha_dev : rt2[blockIdx.y / C];
     const int col0 = blockIdx.x * LB;
     for (int idx = threadIdx.x; idx < LB * H; idx += 256) {
         const int k = idx / LB, l = idx - k * LB;                 // adjacent lanes -> adjacent columns
@@ -181,11 +183,34 @@ hipError_t launch_ot_ode_vec_blur(const DegView& d, const float* x, const float*
     const size_t lds_w = (size_t)(2 * lbw + 1) * W * sizeof(float2), lds_h = (size_t)(2 * lbh + 1) * H * sizeof(float2);
     hipLaunchKernelGGL(fft_rows_fwd_kernel, dim3((H + lbw - 1) / lbw, B * C), dim3(256), lds_w, s, y, (const float*)buf1, z, H, W, ilog2_exact(W), lbw);
     hipLaunchKernelGGL(fft_cols_solve_kernel, dim3((W + lbh - 1) / lbh, B * C), dim3(256), lds_h, s, z, (const float*)pw_h, (const float*)pw_w, rt2,
-                       sigma2, C, H, W, ilog2_exact(H), lbh);
+                       (const double*)nullptr, sigma2, C, H, W, ilog2_exact(H), lbh);
     hipLaunchKernelGGL(fft_rows_inv_kernel, dim3((H + lbw - 1) / lbw, B * C), dim3(256), lds_w, s, (const float2*)z, buf0, H, W, ilog2_exact(W), lbw);
     r = hipGetLastError();
     if (r != hipSuccess) return r;
     return launch_deg_Hadj(d, buf0, vec, B, C, H, W, buf1, s);                                        // vec = H_adj(sol), ot_ode.py:130
+}
+
+hipError_t launch_blur_power_spectrum(const DegView& d, int H, int W, float* pw_h, float* pw_w, hipStream_t s) {
+    if (d.kind != DEG_BLUR || !d.taps || H > 2048 || W > 2048 || d.ntaps > H || d.ntaps > W) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(blur_power_spectrum_kernel, dim3((H + 63) / 64), dim3(64), 0, s, d.taps, d.ntaps, H, pw_h);
+    hipLaunchKernelGGL(blur_power_spectrum_kernel, dim3((W + 63) / 64), dim3(64), 0, s, d.taps, d.ntaps, W, pw_w);
+    return hipGetLastError();
+}
+
+// Prox-PnP's Fourier-domain prox of the Gaussian data term for the circular blur (pnp_gs.py:36-44):
+//     out = real( ifft2( fft2(in) / (alpha |fft2 filter|^2 + 1) ) ),  in = alpha H_adj(y) + y'
+// the same three launches as the OT-ODE solve; alpha is read on the device.  cplx: 2*B*C*H*W floats
+hipError_t launch_fft_prox_blur(const float* in, const double* alpha_dev, const float* pw_h, const float* pw_w, float* out, int B, int C, int H, int W,
+                                float* cplx, hipStream_t s) {
+    if (!in || !alpha_dev || !pw_h || !pw_w || !out || !cplx || H > 2048 || W > 2048) return hipErrorInvalidValue;
+    float2* z = reinterpret_cast<float2*>(cplx);
+    const int lbw = lines_per_wg(W), lbh = lines_per_wg(H);
+    const size_t lds_w = (size_t)(2 * lbw + 1) * W * sizeof(float2), lds_h = (size_t)(2 * lbh + 1) * H * sizeof(float2);
+    hipLaunchKernelGGL(fft_rows_fwd_kernel, dim3((H + lbw - 1) / lbw, B * C), dim3(256), lds_w, s, in, (const float*)nullptr, z, H, W, ilog2_exact(W), lbw);
+    hipLaunchKernelGGL(fft_cols_solve_kernel, dim3((W + lbh - 1) / lbh, B * C), dim3(256), lds_h, s, z, pw_h, pw_w, (const float*)nullptr, alpha_dev, 1.0f,
+                       C, H, W, ilog2_exact(H), lbh);
+    hipLaunchKernelGGL(fft_rows_inv_kernel, dim3((H + lbw - 1) / lbw, B * C), dim3(256), lds_w, s, (const float2*)z, out, H, W, ilog2_exact(W), lbw);
+    return hipGetLastError();
 }
 
 }  // namespace pf

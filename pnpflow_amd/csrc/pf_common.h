@@ -292,6 +292,28 @@ hipError_t launch_rk_norm(const float* a, const float* b, const float* y0, const
 hipError_t launch_rk_interp(const float* y0, const float* y1, const float* ymid, const float* k0, const float* k6, float sign, float dt, float x, float* out,
                             int64_t n, hipStream_t s);
 
+// ---- Prox-PnP with the gradient-step denoiser: glue (prox_pnp.hip) and the Fourier prox (fft2.hip) ---------------------------
+enum { PNPGS_DG = 0, PNPGS_PGD = 1, PNPGS_HQS_MASK = 2, PNPGS_HQS_BLUR = 3 };      // output form of launch_pnpgs_combine
+constexpr int PNPGS_MAX_PARTS = 256;
+int pnpgs_parts(int64_t n4);         // fp64 partial sums per tensor for n4 float4 lanes (<= PNPGS_MAX_PARTS)
+// r = x - N; partial (or nullptr): pnpgs_parts(n / 4) partials of sum r^2
+hipError_t launch_pnpgs_seed(const float* x, const float* N, float* r, double* partial, int64_t n, hipStream_t s);
+// one pass over z, N, JN ([B][n]) -> out in the form `mode`; aux: the measurement (HQS_MASK) / H_adj(measurement) (HQS_BLUR);
+// mask: [B][hw] bytes (HQS_MASK; hw % 4 == 0); alpha_dev: device double (PGD, HQS_BLUR)
+hipError_t launch_pnpgs_combine(int mode, const float* z, const float* N, const float* JN, const float* aux, const uint8_t* mask, const double* alpha_dev,
+                                float* out, int B, int64_t n, int64_t hw, hipStream_t s);
+// pnpgs_parts(n / 4) partials of sum (a - b)^2; copy_to (or nullptr) <- a
+hipError_t launch_pnpgs_sqdist(const float* a, const float* b, float* copy_to, double* partial, int64_t n, hipStream_t s);
+hipError_t launch_pnpgs_sum(const double* partial, int nparts, double scale, double* out, hipStream_t s);
+// alpha *= 0.9 when 0.5 (sum p_new - e_prev) < 0.1 / alpha sum p_dx; e_prev <- sum p_new; log[2 iter] = (gap, threshold) when given
+hipError_t launch_pnpgs_decide(const double* p_new, int np_new, const double* p_dx, int np_dx, double* e_prev, double* alpha_dev, const int* iter, double* log,
+                               int max_iter, hipStream_t s);
+// pw_h[H], pw_w[W] <- the separable factors of |fft2(blur filter)|^2
+hipError_t launch_blur_power_spectrum(const DegView& d, int H, int W, float* pw_h, float* pw_w, hipStream_t s);
+// out = real(ifft2(fft2(in) / (alpha |fft2 filter|^2 + 1))), alpha read from a device double; cplx: 2*B*C*H*W floats
+hipError_t launch_fft_prox_blur(const float* in, const double* alpha_dev, const float* pw_h, const float* pw_w, float* out, int B, int C, int H, int W,
+                                float* cplx, hipStream_t s);
+
 // ---- NCSN++ ("rectified") velocity net, the ops that are not convs (ncsnpp_ops.hip) ----------------------------------------
 // FIR resampling of an NHWC activation (upfirdn2d of up_or_down_sampling.py:204-259 on every channel), optionally of TWO views of
 // the same source in one pass: `out_act` takes act(GroupNorm(src)) (the per-image sc/sh of `coef`, SiLU), `out_raw` the raw

@@ -82,7 +82,8 @@ def merge_cfg_from_list(cfg: CfgNode, cfg_list: List[str]) -> CfgNode:
 
 # ---- model factory / loader (reference pnpflow/utils.py:170-240) ----------------------------
 def define_model(args):
-    if args.model in ("ot", "indep"):
+    if args.model in ("ot", "indep", "gradient_step"):
+        # "gradient_step": the denoiser net of Prox-PnP is the same U-Net (utils.py:170-180 of the reference); its second input is the noise level
         model = UNet(input_channels=args.num_channels, input_height=args.dim_image, ch=32, ch_mult=(1, 2, 4, 8),
                      num_res_blocks=6, attn_resolutions=(16, 8), resamp_with_conv=True,
                      device_index=int(getattr(args, "device_index", 0)))
@@ -101,7 +102,7 @@ def define_model(args):
             raise Exception("the rectified model exists for celebahq and afhq_cat")
         score_model = mutils.create_model(config, device_index=int(getattr(args, "device_index", 0)))
         return score_model, dict(model=score_model, step=0)
-    raise Exception("Unknown model! (this engine implements the 'ot'/'indep' U-Net and the 'rectified' NCSN++ velocity fields)")
+    raise Exception("Unknown model! (this engine implements the 'ot'/'indep' U-Net, the 'rectified' NCSN++ velocity fields and the 'gradient_step' denoiser U-Net)")
 
 
 def load_model(name_model, model, state, download=False, checkpoint_path=None, dataset=None, device='cuda'):
@@ -111,11 +112,14 @@ def load_model(name_model, model, state, download=False, checkpoint_path=None, d
         state['model'].load_state_dict(loaded_state['model'], strict=False)
         state['step'] = loaded_state.get('step', 0)
         return state
-    if name_model not in ("ot", "indep"):
+    if name_model not in ("ot", "indep", "gradient_step"):
         raise NotImplementedError(name_model)
     if download:
         raise RuntimeError("no network: place the reference's model_final.pt at checkpoint_path")
-    model.load_state_dict(torch.load(checkpoint_path, map_location='cpu'))
+    sd = torch.load(checkpoint_path, map_location='cpu')
+    if name_model == "gradient_step" and isinstance(sd, dict) and "model_state_dict" in sd:
+        sd = sd["model_state_dict"]         # a per-epoch training checkpoint (train_denoiser.py:215-218); the final one is a plain state dict (:255-256)
+    model.load_state_dict(sd)
     model.to(device)
 
 
