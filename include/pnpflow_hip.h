@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PF_ABI_VERSION 5
+#define PF_ABI_VERSION 6
 
 typedef enum pf_status {
     PF_OK = 0,
@@ -182,6 +182,10 @@ int pf_fill_normal(float* out, int64_t n, uint64_t seed, uint64_t stream_id, voi
  * single-device run at the global batch size draws for those images (replaces the one torch.randn_like(x) over the whole
  * batch of interpolation_step, pnpflow/methods/pnp_flow.py:47-48, when the batch is split over GPUs). */
 int pf_fill_normal_at(float* out, int64_t n, uint64_t seed, uint64_t stream_id, uint64_t elem_offset, void* stream);
+/* fills out[n] with +-1.0f (Rademacher) from the same Philox4x32-10 words: out[i] = element e = elem_offset + i of the stream, which is
+ * word e % 4 of counter (e/4 lo, e/4 hi, stream_id lo, stream_id hi) under key (seed lo, seed hi); +1 when the word's top bit is set, else -1.
+ * Replaces torch.randint_like(data, low=0, high=2).float() * 2 - 1 (pnpflow/utils.py:251, image_generation/likelihood.py:168). */
+int pf_fill_rademacher(float* out, int64_t n, uint64_t seed, uint64_t stream_id, uint64_t elem_offset, void* stream);
 
 /* per-image PSNR of postprocess(rec) vs postprocess(clean), data_range 1
  * (pnpflow/utils.py:560-577, 594-611) -> out[B] (device). */
@@ -305,6 +309,42 @@ typedef struct pf_dopri5_params {
     int32_t reserved0;
 } pf_dopri5_params;
 int pf_flow_ode_dopri5(pf_engine* e, const pf_dopri5_params* prm, const float* x_in, float* x_out, int B, int64_t* stats, void* stream);
+
+/* ---- the prior itself: Hutchinson divergence, sampling, log-likelihood -----------------------------------------------------------
+ * Value of the Hutchinson-Skilling trace estimator (utils.hut_estimator, pnpflow/utils.py:243-270; get_div_fn,
+ * image_generation/likelihood.py:27-38): div[b] = eps_b . (J_v(x, t) eps)_b = eps_b . (J_v(x, t)^T eps)_b - one retained forward at (x, t), one
+ * hand-written backward with vec = eps, then a deterministic per-image dot product (fp64 per-block partials, fixed-order finish).  The
+ * net sees t * the solver time scale.  A VALUE only: the gradient of the trace term with respect to x (what Flow-Priors differentiates,
+ * hut_estimator(create_graph=True)) is a second-order pass the engine does not have.
+ * t: device [B]; eps: [B,C,H,W]; v_out: [B,C,H,W] or NULL (the velocity v(x, t)); div_out: device double[B].  Afterwards the retained
+ * forward (pf_unet_backward) is that of (x, t). */
+int pf_flow_divergence(pf_engine* e, const float* x, const float* t, const float* eps, float* v_out, double* div_out, int B, void* stream);
+
+/* torchdiffeq's fixed-grid `euler` over host_t[0 .. n_points - 1] (FLOW_MATCHING.generate_samples, pnpflow/train_flow_matching.py:170-198):
+ *   x += (host_t[i+1] - host_t[i]) * v(x, host_t[i]),  the difference in fp32, a separate multiply and add.
+ * Nothing synchronises inside the loop.  x_in, x_out: [B,C,H,W] (may alias); n_points >= 2. */
+int pf_flow_ode_euler(pf_engine* e, const float* host_t, int n_points, const float* x_in, float* x_out, int B, void* stream);
+
+/* The log-likelihood solve of get_likelihood_fn_rf (image_generation/likelihood.py:172-193): the augmented state (x, logp[B]) with
+ *   dx/dt = v(x, t),  d logp_b/dt = eps_b . (J_v(x, t)^T eps)_b
+ * from t0 to t1 under scipy.integrate.solve_ivp(method='RK45')'s rules (csrc/rk45_control.h): Dormand-Prince 5(4), the RMS error norm over
+ * all B*C*H*W + B entries with scale atol + rtol max(|y|, |y_new|), SciPy's initial step, the last step clipped onto t1.  x is carried in
+ * fp32, logp in fp64 on the device; time and step in fp64 on the host, the net is fed float(t) * the solver time scale.  Per attempt: six
+ * VJP evaluations (FSAL) and one 8-byte read of the error norm.
+ *   z_out: [B,C,H,W] the state at t1;  delta_logp: device double[B];  bpd: device float[B] or NULL,
+ *   bpd[b] = -(-N/2 ln(2 pi) - 1/2 |z_b|^2 + delta_logp[b]) / (N ln 2) + offset,  N = C*H*W
+ *   stats (host int64[3], may be NULL): accepted steps, rejected steps, evaluations (2 + 6 * attempts)
+ * More than max_attempts attempts, a step below SciPy's min_step (10 ulp of t) or a non-finite error norm fail with PF_ERR_NUMERIC and no
+ * result.  Afterwards the retained forward is that of the last evaluation.  Synchronises `stream`. */
+typedef struct pf_likelihood_params {
+    double t0, t1;
+    double rtol, atol;
+    double offset;
+    int32_t max_attempts;
+    int32_t reserved0;
+} pf_likelihood_params;
+int pf_flow_likelihood_rk45(pf_engine* e, const pf_likelihood_params* prm, const float* x_in, const float* eps, float* z_out, double* delta_logp,
+                            float* bpd, int64_t* stats, int B, void* stream);
 
 /* ---- whole restoration loop --------------------------------------------------------- */
 typedef struct pf_pnp_params {

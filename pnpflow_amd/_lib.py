@@ -12,7 +12,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PNPFLOW_HIP_LIB") or os.path.join(_HERE, "libpnpflow_hip.so")   # override: A/B builds of the kernels
 
-PF_ABI_VERSION = 5
+PF_ABI_VERSION = 6
 
 PF_DEG_DENOISING, PF_DEG_BOX_INPAINTING, PF_DEG_MASK_INPAINTING, PF_DEG_SUPERRESOLUTION, PF_DEG_GAUSSIAN_BLUR, PF_DEG_SR_FILTERED = range(6)
 
@@ -59,6 +59,11 @@ class PfDopri5Params(C.Structure):
                 ("reserved0", C.c_int32)]
 
 
+class PfLikelihoodParams(C.Structure):
+    _fields_ = [("t0", C.c_double), ("t1", C.c_double), ("rtol", C.c_double), ("atol", C.c_double), ("offset", C.c_double),
+                ("max_attempts", C.c_int32), ("reserved0", C.c_int32)]
+
+
 class PfPnpGsParams(C.Structure):
     _fields_ = [("algo", C.c_int32), ("noise_model", C.c_int32), ("max_iter", C.c_int32), ("first", C.c_int32), ("stop", C.c_int32),
                 ("skip_grad_step", C.c_int32), ("host_sigma_den", C.POINTER(C.c_float)), ("grad_coef", C.c_float), ("use_graph", C.c_int32),
@@ -99,6 +104,7 @@ SIGNATURES = {
     "pf_denoise_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p]),
     "pf_fill_normal": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p]),
     "pf_fill_normal_at": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "pf_fill_rademacher": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]),
     "pf_attention_core": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "pf_psnr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "pf_upfirdn2d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 13 + [C.c_void_p]),
@@ -115,6 +121,10 @@ SIGNATURES = {
     "pf_d_flow_value_and_grad": (C.c_int, [C.c_void_p, C.POINTER(PfDegradation), C.POINTER(PfDFlowParams), C.c_void_p, C.c_void_p, C.c_float,
                                            C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pf_flow_ode_dopri5": (C.c_int, [C.c_void_p, C.POINTER(PfDopri5Params), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_void_p]),
+    "pf_flow_divergence": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "pf_flow_ode_euler": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "pf_flow_likelihood_rk45": (C.c_int, [C.c_void_p, C.POINTER(PfLikelihoodParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
     "pf_gs_denoiser_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pf_pnp_gs_restore": (C.c_int, [C.c_void_p, C.POINTER(PfDegradation), C.POINTER(PfPnpGsParams), C.c_void_p, C.c_void_p, C.POINTER(C.c_double),
                                     C.POINTER(C.c_double), C.c_int, C.c_void_p, ITER_CB, C.c_void_p]),

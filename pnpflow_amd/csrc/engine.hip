@@ -19,6 +19,7 @@
 #include "../../include/pnpflow_hip.h"
 #include "pf_common.h"
 #include "weight_pack.h"
+#include "rk45_control.h"
 
 using namespace pf;
 
@@ -129,6 +130,7 @@ struct NxMod {                 // one entry of NCSNpp.all_modules (ncsnpp.py:72-
 
 struct DFlowState;                 // D-Flow / dopri5 buffers and graphs (engine_dflow.inc)
 struct PnpGsState;                 // Prox-PnP (gradient-step denoiser) buffers and graph (engine_pnp_gs.inc)
+struct PriorEvalState;             // divergence / Euler sampler / likelihood solve buffers (engine_prior_eval.inc)
 
 struct pf_engine {
     int device = 0;
@@ -177,6 +179,7 @@ struct pf_engine {
     const void* held_plans[3] = {};      // plans a cached D-Flow graph replays (kept out of the plan cache's eviction)
     PnpGsState* pnpgs = nullptr;         // pf_gs_denoiser_grad / pf_pnp_gs_restore state (engine_pnp_gs.inc)
     const void* held_pnpgs_plan = nullptr;   // the plan its cached graph replays (kept out of the eviction as well)
+    PriorEvalState* prior = nullptr;     // pf_flow_divergence / pf_flow_ode_euler / pf_flow_likelihood_rk45 state (engine_prior_eval.inc)
     // profiling
     bool profile = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
@@ -1511,6 +1514,7 @@ static void drop_dflow_graphs(pf_engine* e);
 static void free_dflow(pf_engine* e);
 static void drop_pnpgs_graph(pf_engine* e);
 static void free_pnpgs(pf_engine* e);
+static void free_prior(pf_engine* e);
 int pf_engine_set_solver_time_scale(pf_engine* e, float scale) {
     if (!e || !(scale > 0.f)) return PF_ERR_INVALID;
     if (scale != e->solver_time_scale) { drop_graph(e); drop_ode_graph(e); drop_dflow_graphs(e); drop_pnpgs_graph(e); e->solver_time_scale = scale; }   // the captured graphs bake the scale in
@@ -1567,6 +1571,7 @@ void pf_engine_destroy(pf_engine* e) {
     free_ode(e);
     free_dflow(e);
     free_pnpgs(e);
+    free_prior(e);
     for (auto& kv : e->plans) for (void* p : kv.second->allocs) hipFree(p);
     for (void* p : e->weight_allocs) hipFree(p);
     for (auto& ev : e->ev_pool) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
@@ -1756,6 +1761,12 @@ int pf_fill_normal(float* out, int64_t n, uint64_t seed, uint64_t stream_id, voi
 int pf_fill_normal_at(float* out, int64_t n, uint64_t seed, uint64_t stream_id, uint64_t elem_offset, void* stream) {
     if (!out || n < 0) return PF_ERR_INVALID;
     LAUNCHCHK(launch_fill_normal(out, n, seed, stream_id, elem_offset, (hipStream_t)stream));
+    return PF_OK;
+}
+int pf_fill_rademacher(float* out, int64_t n, uint64_t seed, uint64_t stream_id, uint64_t elem_offset, void* stream) {
+    if (!out || n < 0) return PF_ERR_INVALID;
+    if (n == 0) return PF_OK;
+    LAUNCHCHK(launch_fill_rademacher(out, n, seed, stream_id, elem_offset, (hipStream_t)stream));
     return PF_OK;
 }
 int pf_attention_core(const float* qkv, float* out, int B, int T, int C, void* stream) {
@@ -2106,3 +2117,4 @@ int pf_engine_profile_read(pf_engine* e, int64_t* launches, double* ms_conv_gemm
 
 #include "engine_dflow.inc"
 #include "engine_pnp_gs.inc"
+#include "engine_prior_eval.inc"

@@ -1,7 +1,9 @@
 // Glue kernels of the two flow solvers built on the velocity net's forward and input-gradient VJP:
 //   * D-Flow (pnpflow/methods/d_flow.py): the explicit-midpoint map T(z) (forward_flow_matching, :41-49), its data term and latent
 //     regulariser (closure, :110-121) and the reverse sweep of T's adjoint;
-//   * the adaptive Dormand-Prince (dopri5) solve of dx/dt = v(x, t) that initialises the latent (inverse_flow_matching, :51-60).
+//   * the adaptive Dormand-Prince (dopri5) solve of dx/dt = v(x, t) that initialises the latent (inverse_flow_matching, :51-60);
+//   * the prior's evaluation (pnpflow/utils.py:243-270 hut_estimator, pnpflow/image_generation/likelihood.py:116-195): the per-image dot
+//     product eps . (J^T eps) of the Hutchinson estimator, the fp64 log-density entries of the augmented RK45 state and the bits/dim finish.
 // NCHW fp32 images; every per-image length is a multiple of 4 (float4 lanes: one thread = 4 consecutive values).
 // Reductions are deterministic: per-block fp64 partial sums (a fixed number of blocks per image / tensor, a fixed tree inside the
 // block) then a fixed-order finish - no float atomics, so replays of one input give bit-identical values (LBFGS's strong-Wolfe line
@@ -183,6 +185,61 @@ __global__ __launch_bounds__(kThreads) void rk_interp4_kernel(const float* __res
     }
 }
 
+// ---- prior evaluation: Hutchinson divergence, augmented RK45 state, bits/dim ---------------------------------------------------------
+// per-image partials of sum(a c)
+__global__ __launch_bounds__(kThreads) void image_dot4_kernel(const float4* __restrict__ a, const float4* __restrict__ c, double* __restrict__ partial, int64_t n4) {
+    __shared__ double sh[kThreads];
+    const int b = blockIdx.y;
+    const float4* ab = a + (size_t)b * n4; const float4* cb = c + (size_t)b * n4;
+    double acc = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n4; i += (int64_t)gridDim.x * kThreads) {
+        const float4 p = ab[i], q = cb[i];
+        acc += (double)(p.x * q.x) + (double)(p.y * q.y) + (double)(p.z * q.z) + (double)(p.w * q.w);
+    }
+    const double s = block_sum(acc, sh);
+    if (threadIdx.x == 0) partial[(size_t)b * gridDim.x + blockIdx.x] = s;
+}
+
+// out[b] = sum of image b's partials, in index order (one thread per image)
+__global__ void image_sum_kernel(const double* __restrict__ partial, int nparts, int B, double* __restrict__ out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double s = 0.0;
+    for (int j = 0; j < nparts; ++j) s += partial[(size_t)b * nparts + j];
+    out[b] = s;
+}
+
+// The B log-density entries of the augmented state, in fp64 (one block; fixed strides and a fixed tree: deterministic):
+//   new_b = logp_b + sum_j step[j] k[j][b],  err_b = sum_j err[j] k[j][b],  scale_b = atol + rtol max(|logp_b|, |new_b|)
+//   sum_out[0] = (sum_x ? sum_x[0] : 0) + sum_b (err_b / scale_b)^2        logp_new (or nullptr) <- new
+__global__ __launch_bounds__(kThreads) void rk_aug_kernel(RkAug c, const double* __restrict__ logp, double* __restrict__ logp_new, double atol, double rtol,
+                                                          const double* __restrict__ sum_x, double* __restrict__ sum_out, int B) {
+    __shared__ double sh[kThreads];
+    double acc = 0.0;
+    for (int b = threadIdx.x; b < B; b += kThreads) {
+        double st = 0.0, er = 0.0;
+        for (int j = 0; j < c.n; ++j) { const double k = c.k[j][b]; st += c.step[j] * k; er += c.err[j] * k; }
+        const double y0 = logp[b], y1 = y0 + st;
+        if (logp_new) logp_new[b] = y1;
+        const double q = er / (atol + rtol * fmax(fabs(y0), fabs(y1)));
+        acc += q * q;
+    }
+    const double s = block_sum(acc, sh);
+    if (threadIdx.x == 0) sum_out[0] = (sum_x ? sum_x[0] : 0.0) + s;
+}
+
+// per image (one thread each, the partials of sum z^2 summed in index order), N = C*H*W:
+//   prior = -N/2 ln(2 pi) - 1/2 sum z^2,   bpd = -(prior + delta_logp) / (N ln 2) + offset        (likelihood.py:144-148, 186-192)
+__global__ void bpd_finish_kernel(const double* __restrict__ pz, int nparts, int B, double N, const double* __restrict__ delta_logp, double offset,
+                                  float* __restrict__ bpd) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double s = 0.0;
+    for (int j = 0; j < nparts; ++j) s += pz[(size_t)b * nparts + j];
+    const double prior = -0.5 * N * 1.8378770664093453 - 0.5 * s;      // ln(2 pi)
+    bpd[b] = (float)(-(prior + delta_logp[b]) / (N * 0.6931471805599453) + offset);
+}
+
 }  // namespace
 
 int reduction_parts(int64_t n4) { return (int)std::max<int64_t>(1, std::min<int64_t>((n4 + kThreads - 1) / kThreads, 64)); }
@@ -243,6 +300,29 @@ hipError_t launch_rk_norm(const float* a, const float* b, const float* y0, const
 hipError_t launch_rk_interp(const float* y0, const float* y1, const float* ymid, const float* k0, const float* k6, float sign, float dt, float x, float* out,
                             int64_t n, hipStream_t s) {
     hipLaunchKernelGGL(rk_interp4_kernel, dim3(stream_blocks(n)), dim3(kThreads), 0, s, y0, y1, ymid, k0, k6, sign, dt, x, out, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_image_dot(const float* a, const float* c, double* partial, double* out, int B, int64_t n, hipStream_t s) {
+    if (n % 4 || B <= 0) return hipErrorInvalidValue;
+    const int np = reduction_parts(n / 4);
+    hipLaunchKernelGGL(image_dot4_kernel, dim3(np, B), dim3(kThreads), 0, s, (const float4*)a, (const float4*)c, partial, n / 4);
+    hipLaunchKernelGGL(image_sum_kernel, dim3((B + 63) / 64), dim3(64), 0, s, (const double*)partial, np, B, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_rk_aug(const RkAug& c, const double* logp, double* logp_new, double atol, double rtol, const double* sum_x, double* sum_out, int B,
+                         hipStream_t s) {
+    if (c.n < 0 || c.n > 7 || B <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rk_aug_kernel, dim3(1), dim3(kThreads), 0, s, c, logp, logp_new, atol, rtol, sum_x, sum_out, B);
+    return hipGetLastError();
+}
+
+hipError_t launch_bpd_finish(const float* z, const double* delta_logp, double* partial, float* bpd, double offset, int B, int64_t n, hipStream_t s) {
+    if (n % 4 || B <= 0) return hipErrorInvalidValue;
+    const int np = reduction_parts(n / 4);
+    hipLaunchKernelGGL(sumsq4_kernel, dim3(np, B), dim3(kThreads), 0, s, (const float4*)z, partial, n / 4);
+    hipLaunchKernelGGL(bpd_finish_kernel, dim3((B + 63) / 64), dim3(64), 0, s, (const double*)partial, np, B, (double)n, delta_logp, offset, bpd);
     return hipGetLastError();
 }
 

@@ -256,6 +256,8 @@ hipError_t launch_interp_iter(const float* z, const float* t, const float* noise
 hipError_t launch_denoise_accum(float* acc, const float* zt, const float* v, const float* t, int mode, float ns,
                                 int B, int n, hipStream_t s);
 hipError_t launch_fill_normal(float* out, int64_t n, uint64_t seed, uint64_t stream_id, uint64_t elem_offset, hipStream_t s);
+// +-1 from the same Philox words: element e is word e % 4 of counter e / 4, +1 when its top bit is set
+hipError_t launch_fill_rademacher(float* out, int64_t n, uint64_t seed, uint64_t stream_id, uint64_t elem_offset, hipStream_t s);
 hipError_t launch_psnr(const float* rec, const float* clean, float* out, int B, int n, hipStream_t s);
 hipError_t launch_fill(float* out, int64_t n, float v, hipStream_t s);
 // FIR resampling / fused bias+activation of the NCSN++ velocity net (fir_ops.hip)
@@ -291,6 +293,15 @@ hipError_t launch_rk_norm(const float* a, const float* b, const float* y0, const
                           double* out, int64_t n, hipStream_t s);
 hipError_t launch_rk_interp(const float* y0, const float* y1, const float* ymid, const float* k0, const float* k6, float sign, float dt, float x, float* out,
                             int64_t n, hipStream_t s);
+// prior evaluation (engine_prior_eval.inc).  out[b] = sum_i a[b][i] c[b][i] in fp64; partial: >= B * 64 doubles
+hipError_t launch_image_dot(const float* a, const float* c, double* partial, double* out, int B, int64_t n, hipStream_t s);
+// the B fp64 log-density entries of the augmented RK45 state: new = logp + sum_j step[j] k[j], error estimate sum_j err[j] k[j] (k[j]: [B])
+struct RkAug { const double* k[7]; double step[7]; double err[7]; int n; };
+// sum_out[0] = (sum_x ? sum_x[0] : 0) + sum_b (err_b / (atol + rtol max(|logp_b|, |new_b|)))^2; logp_new (or nullptr) <- new
+hipError_t launch_rk_aug(const RkAug& c, const double* logp, double* logp_new, double atol, double rtol, const double* sum_x, double* sum_out, int B,
+                         hipStream_t s);
+// bpd[b] = -(-N/2 ln(2 pi) - 1/2 |z_b|^2 + delta_logp[b]) / (N ln 2) + offset, N = n; partial: >= B * 64 doubles
+hipError_t launch_bpd_finish(const float* z, const double* delta_logp, double* partial, float* bpd, double offset, int B, int64_t n, hipStream_t s);
 
 // ---- Prox-PnP with the gradient-step denoiser: glue (prox_pnp.hip) and the Fourier prox (fft2.hip) ---------------------------
 enum { PNPGS_DG = 0, PNPGS_PGD = 1, PNPGS_HQS_MASK = 2, PNPGS_HQS_BLUR = 3 };      // output form of launch_pnpgs_combine

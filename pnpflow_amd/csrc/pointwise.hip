@@ -550,6 +550,30 @@ hipError_t launch_fill_normal(float* out, int64_t n, uint64_t seed, uint64_t str
     return hipGetLastError();
 }
 
+// Rademacher draw from the normals' Philox words: element e of the stream is word e % 4 of counter (e/4 lo, e/4 hi, stream lo, stream hi),
+// key (seed lo, seed hi); +1 when the word's top bit is set, else -1.  One thread per counter; out[i] = element elem_offset + i.
+__global__ __launch_bounds__(256) void fill_rademacher_kernel(float* out, int64_t n, uint64_t seed, uint64_t stream, uint64_t elem_offset) {
+    const uint64_t q_lo = elem_offset >> 2;
+    const int64_t nq = (int64_t)(((elem_offset + (uint64_t)n + 3) >> 2) - q_lo);
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < nq; q += (int64_t)gridDim.x * 256) {
+        const uint64_t ctr = q_lo + (uint64_t)q;
+        uint32_t r[4];
+        philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)stream, (uint32_t)(stream >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), r);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint64_t el = ctr * 4 + (uint64_t)j;
+            if (el >= elem_offset && el - elem_offset < (uint64_t)n) out[el - elem_offset] = (r[j] >> 31) ? 1.0f : -1.0f;
+        }
+    }
+}
+
+hipError_t launch_fill_rademacher(float* out, int64_t n, uint64_t seed, uint64_t stream_id, uint64_t elem_offset, hipStream_t s) {
+    if (n <= 0) return hipErrorInvalidValue;
+    const int64_t nq = (int64_t)(((elem_offset + (uint64_t)n + 3) >> 2) - (elem_offset >> 2));
+    hipLaunchKernelGGL(fill_rademacher_kernel, dim3((unsigned)std::min<int64_t>((nq + 255) / 256, 4096)), dim3(256), 0, s, out, n, seed, stream_id, elem_offset);
+    return hipGetLastError();
+}
+
 // z_tilde = t*z + (1-t)*eps   (pnp_flow.py:47-48).  The batch is one flat noise stream:
 // element e of the [B*n] tensor uses normal number e of stream `stream_id`.
 __global__ __launch_bounds__(256) void interpolate_kernel(const float* z, const float* t, const float* noise, uint64_t seed,

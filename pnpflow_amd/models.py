@@ -100,6 +100,61 @@ class _EngineNet:
         v = self.forward_retain(x, temp)
         return v, self.backward(vec)
 
+    # ---- the prior itself: divergence estimate, fixed-grid sampling, log-likelihood solve --------
+    def _check_images(self, x: torch.Tensor, what: str):
+        Hh = self.input_height
+        if x.ndim != 4 or tuple(x.shape[1:]) != (self.input_channels, Hh, Hh):
+            raise ValueError(f"{what} of shape {tuple(x.shape)} does not match the net's (B, {self.input_channels}, {Hh}, {Hh})")
+        if not x.is_cuda:
+            raise _lib.PnpFlowHipError(f"{type(self).__name__} needs GPU tensors (there is no CPU path)")
+        return x.detach().contiguous().float()
+
+    def divergence(self, x: torch.Tensor, temp: torch.Tensor, eps: torch.Tensor, return_velocity: bool = False):
+        """Value of the Hutchinson estimator eps . (J_v(x, t) eps) per image, (B,) fp64 (pf_flow_divergence: one retained forward, one
+        backward with vec = eps, a deterministic dot product).  The net sees t * the solver time scale.  No autograd graph."""
+        x = self._check_images(x, "input"); eps = self._check_images(eps, "eps")
+        B = x.shape[0]
+        if eps.shape != x.shape:
+            raise ValueError(f"eps of shape {tuple(eps.shape)} for an input of shape {tuple(x.shape)}")
+        t = torch.as_tensor(temp, dtype=torch.float32, device=x.device).reshape(-1)
+        t = (t.expand(B) if t.numel() == 1 else t).contiguous()
+        if t.numel() != B:
+            raise ValueError(f"t has {t.numel()} entries for a batch of {B}")
+        div = torch.empty(B, dtype=torch.float64, device=x.device)
+        v = torch.empty_like(x) if return_velocity else None
+        _lib.check(self._lib.pf_flow_divergence(self._h, x.data_ptr(), t.data_ptr(), eps.data_ptr(), v.data_ptr() if return_velocity else None,
+                                                div.data_ptr(), B, _lib.current_stream_ptr()), self._h, "pf_flow_divergence")
+        return (div, v) if return_velocity else div
+
+    def euler(self, x: torch.Tensor, time_points) -> torch.Tensor:
+        """torchdiffeq's fixed-grid euler over `time_points` (fp32): x += (t[i+1] - t[i]) * v(x, t[i]) (pf_flow_ode_euler)."""
+        x = self._check_images(x, "input")
+        grid = np.ascontiguousarray(torch.as_tensor(time_points).detach().cpu().to(torch.float32).numpy().reshape(-1))
+        if grid.size < 2:
+            raise ValueError("the time grid needs at least 2 points")
+        out = torch.empty_like(x)
+        _lib.check(self._lib.pf_flow_ode_euler(self._h, grid.ctypes.data_as(C.POINTER(C.c_float)), int(grid.size), x.data_ptr(), out.data_ptr(),
+                                               x.shape[0], _lib.current_stream_ptr()), self._h, "pf_flow_ode_euler")
+        return out
+
+    def likelihood_ode(self, x: torch.Tensor, eps: torch.Tensor, t0: float = 1.0, t1: float = 1e-5, rtol: float = 1e-5, atol: float = 1e-5,
+                       offset: float = 7.0, max_attempts: int = 1000):
+        """The augmented solve (x, logp) of get_likelihood_fn_rf under SciPy's RK45 rules (pf_flow_likelihood_rk45) ->
+        (z (B,C,H,W), delta_logp (B,) fp64, bpd (B,) fp32, dict(accepted, rejected, nfev))."""
+        x = self._check_images(x, "input"); eps = self._check_images(eps, "eps")
+        if eps.shape != x.shape:
+            raise ValueError(f"eps of shape {tuple(eps.shape)} for an input of shape {tuple(x.shape)}")
+        B = x.shape[0]
+        prm = _lib.PfLikelihoodParams()
+        prm.t0, prm.t1, prm.rtol, prm.atol, prm.offset, prm.max_attempts = float(t0), float(t1), float(rtol), float(atol), float(offset), int(max_attempts)
+        z = torch.empty_like(x)
+        dlp = torch.empty(B, dtype=torch.float64, device=x.device)
+        bpd = torch.empty(B, dtype=torch.float32, device=x.device)
+        stats = (C.c_int64 * 3)()
+        _lib.check(self._lib.pf_flow_likelihood_rk45(self._h, C.byref(prm), x.data_ptr(), eps.data_ptr(), z.data_ptr(), dlp.data_ptr(), bpd.data_ptr(),
+                                                     stats, B, _lib.current_stream_ptr()), self._h, "pf_flow_likelihood_rk45")
+        return z, dlp, bpd, dict(accepted=int(stats[0]), rejected=int(stats[1]), nfev=int(stats[2]))
+
     # ---- debugging: named internal activations of the last forward (NCHW numpy) -----------
     def read_taps(self, B):
         """Internal activations of the last forward as {name: (B,C,H,W) numpy}.  Only

@@ -123,6 +123,79 @@ def load_model(name_model, model, state, download=False, checkpoint_path=None, d
     model.to(device)
 
 
+# ---- Hutchinson trace estimator (reference pnpflow/utils.py:243-270) --------------------------
+_device_draws = 0
+
+
+def device_draw(kind, shape, device, seed=None, stream_id=None):
+    """A (shape) fp32 tensor of engine draws on `device`: kind 'rademacher' (+-1, pf_fill_rademacher) or 'gaussian' (pf_fill_normal).
+    seed defaults to torch.initial_seed() (what torch.manual_seed set), stream_id to a per-process draw counter."""
+    global _device_draws
+    if stream_id is None:
+        stream_id = _device_draws
+        _device_draws += 1
+    seed = (torch.initial_seed() if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF
+    out = torch.empty(tuple(shape), dtype=torch.float32, device=device)
+    if not out.is_cuda:
+        raise _lib.PnpFlowHipError("device_draw needs a GPU device (there is no CPU path)")
+    lib = _lib.load()
+    with torch.cuda.device(out.device):
+        if kind == "rademacher":
+            _lib.check(lib.pf_fill_rademacher(out.data_ptr(), out.numel(), seed, int(stream_id), 0, _lib.current_stream_ptr()), None, "pf_fill_rademacher")
+        elif kind == "gaussian":
+            _lib.check(lib.pf_fill_normal(out.data_ptr(), out.numel(), seed, int(stream_id), _lib.current_stream_ptr()), None, "pf_fill_normal")
+        else:
+            raise NotImplementedError(f"draw kind {kind!r} unknown ('rademacher' or 'gaussian')")
+    return out
+
+
+def _velocity_net(v):
+    """(engine net, time scale) behind `v`: the net itself (v(x, t) feeds t as it is), or a bound method such as a solver's
+    model_forward, whose object holds the net as `.model` and, for the 'rectified' NCSN++ net, feeds it t * 999."""
+    if hasattr(v, "divergence") and hasattr(v, "handle"):
+        return v, 1.0
+    owner = getattr(v, "__self__", None)
+    net = getattr(owner, "model", None)
+    if net is None or not hasattr(net, "divergence"):
+        raise TypeError("hut_estimator: `v` must be an engine net (UNet / NCSNpp) or a bound method of an object that holds one as `.model`")
+    rectified = getattr(getattr(owner, "args", None), "model", None) == "rectified"
+    return net, 999.0 if rectified else 1.0
+
+
+def hut_estimator(NO_test, v, inp, t, eps=None):
+    """Value of the Hutchinson trace estimator of the velocity field's Jacobian at (inp, t) (reference pnpflow/utils.py:243-270):
+    mean over NO_test draws of eps . (J eps), shape (B,), fp32.  Since eps . (J eps) = eps . (J^T eps), each draw is one engine call
+    (pf_flow_divergence: retained forward, hand-written backward with vec = eps, per-image dot product) - exact, no forward mode.
+
+    `v`: the engine net, or a bound method of an object that holds one as `.model` (a solver's model_forward).  `eps`: optional
+    (NO_test, B, C, H, W) (or (B, C, H, W) when NO_test is 1) probe vectors; otherwise NO_test Rademacher draws from the device fill.
+
+    The result is a plain VALUE WITHOUT AN AUTOGRAD GRAPH.  The reference builds it with create_graph=True so that Flow-Priors can take
+    the trace term's gradient with respect to `inp`; that second-order pass does not exist in this engine, so Flow-Priors cannot be
+    built on this function."""
+    net, scale = _velocity_net(v)
+    NO_test = int(NO_test)
+    if NO_test < 1:
+        raise ValueError(f"NO_test must be >= 1, not {NO_test}")
+    if inp.ndim != 4:
+        raise ValueError(f"Expected input `inp` to be an 4D tensor, but got {tuple(inp.shape)}")
+    B = inp.shape[0]
+    if eps is not None:
+        eps = torch.as_tensor(eps)
+        if eps.ndim == 4 and NO_test == 1:
+            eps = eps[None]
+        if tuple(eps.shape) != (NO_test,) + tuple(inp.shape):
+            raise ValueError(f"eps of shape {tuple(eps.shape)} does not match (NO_test, B, C, H, W) = {(NO_test,) + tuple(inp.shape)}")
+    if hasattr(net, "set_solver_time_scale"):
+        net.set_solver_time_scale(scale)
+    tt = torch.as_tensor(t, dtype=torch.float32).reshape(-1)
+    total = torch.zeros(B, dtype=torch.float64, device=inp.device)
+    for i in range(NO_test):
+        e = eps[i].to(inp.device) if eps is not None else device_draw("rademacher", inp.shape, inp.device)
+        total += net.divergence(inp, tt, e)
+    return (total / NO_test).float()
+
+
 # ---- metric (reference pnpflow/utils.py:560-577, 594-674) ------------------------------------
 def draw_measurement_noise(batch, gshape, lo, hi, device, source="cpu"):
     """The `torch.manual_seed(batch); torch.randn_like(noisy_img)` draw of pnp_flow.py:79-80 / ot_ode.py:44-45 for images [lo, hi) of a
