@@ -315,7 +315,8 @@ int pf_flow_ode_dopri5(pf_engine* e, const pf_dopri5_params* prm, const float* x
  * image_generation/likelihood.py:27-38): div[b] = eps_b . (J_v(x, t) eps)_b = eps_b . (J_v(x, t)^T eps)_b - one retained forward at (x, t), one
  * hand-written backward with vec = eps, then a deterministic per-image dot product (fp64 per-block partials, fixed-order finish).  The
  * net sees t * the solver time scale.  A VALUE only: the gradient of the trace term with respect to x (what Flow-Priors differentiates,
- * hut_estimator(create_graph=True)) is a second-order pass the engine does not have.
+ * hut_estimator(create_graph=True)) is a second-order pass the engine does not have; pf_flow_priors_grad obtains it from two of these
+ * first-order VJPs instead.
  * t: device [B]; eps: [B,C,H,W]; v_out: [B,C,H,W] or NULL (the velocity v(x, t)); div_out: device double[B].  Afterwards the retained
  * forward (pf_unet_backward) is that of (x, t). */
 int pf_flow_divergence(pf_engine* e, const float* x, const float* t, const float* eps, float* v_out, double* div_out, int B, void* stream);
@@ -412,6 +413,52 @@ typedef struct pf_pnp_gs_params {
 } pf_pnp_gs_params;
 int pf_pnp_gs_restore(pf_engine* e, const pf_degradation* d, const pf_pnp_gs_params* prm, const float* y, float* x_inout, double* host_alpha_out,
                       double* host_log, int B, void* stream, pf_iter_callback iter_cb, void* user);
+
+/* ---- Flow-Priors (pnpflow/methods/flow_priors.py) -----------------------------------------------------------------------------
+ * Per outer iteration i of N: t = i/N (1 - eps0) + eps0 (eps0 = start_time, or 1e-3 with dt = 1/N when start_time <= 0), a fresh Adam
+ * (lr = eta, betas (0.9, 0.999), eps 1e-8), K inner steps on
+ *   loss(x) = lmbda |H(x + v(x, t) dt) - y_next|^2 (gaussian) | lmbda |.|_1 (laplace)  +  dt eps . J_v(x, t) eps  (+ 0.5 |x|^2 on iteration 0),
+ *   y_next = (t + dt) y + (1 - (t + dt)) H(x_init),
+ * the detached grad_xt_lik = -1/(1 - t) (-x + t v(x, t)) added to the gradient on every later iteration, then x += v(x, t) dt.
+ * The gradient of the trace term is the central difference of two first-order VJPs (flow_priors.py differentiates hut_estimator's
+ * jvp a second time):  dt (J(x + h eps)^T eps - J(x - h eps)^T eps) / (2 h),  h = fd_step;  O(h^2) truncation.  Per inner step: three retained
+ * forwards and three backwards.  The net sees t * time_scale (999 for the NCSN++ net). */
+typedef struct pf_flow_priors_params {
+    int32_t N;                /* outer iterations (>= 1) */
+    int32_t K;                /* Adam steps per outer iteration (>= 1) */
+    int32_t first;            /* pf_flow_priors_restore runs outer iterations [first, stop) ... */
+    int32_t stop;             /* ... 0 = N */
+    double lmbda;
+    double eta;               /* Adam's lr */
+    double start_time;        /* < 1 */
+    double fd_step;           /* h > 0 of the central difference */
+    int32_t noise_model;      /* 0 gaussian | 1 laplace */
+    int32_t reserved0;
+    uint64_t seed;            /* Philox key of the engine's Rademacher probes (pf_fill_rademacher) */
+    uint64_t stream_base;     /* probe of inner step k of outer iteration i: stream id stream_base + i * K + k, element offset 0 */
+    double time_scale;        /* label = t * time_scale (> 0) */
+} pf_flow_priors_params;
+
+/* One Adam step of torch.optim.Adam's single-tensor form on device arrays of n values (any n, any alignment): step >= 1 is the
+ * optimiser's step count after the update; the bias corrections are computed in double on the host (csrc/adam_step.h). */
+int pf_adam_step(float* x, float* m, float* v, const float* g, int64_t n, double lr, double beta1, double beta2, double eps, int step, void* stream);
+
+/* The gradient of one inner step of outer iteration `iteration` at x with the probe eps ([B,C,H,W], +-1), no update:
+ *   out_g_data = w + dt J(x)^T w,  w = H_adj(2 lmbda r) | H_adj(lmbda sign r),  r = H(x + pred dt) - y_next
+ *   out_g_trace = dt (J(x + h eps)^T eps - J(x - h eps)^T eps) / (2 h)
+ *   out_g = out_g_data + out_g_trace + (x when iteration == 0, else grad_xt_lik);  out_pred = v(x, t)
+ * Any of the four outputs may be NULL.  x, x_init: [B,C,H,W]; y: [B,C,Hy,Wy]. */
+int pf_flow_priors_grad(pf_engine* e, const pf_degradation* d, const pf_flow_priors_params* prm, const float* x, const float* x_init, const float* y,
+                        const float* eps, int iteration, float* out_g, float* out_g_data, float* out_g_trace, float* out_pred, int B, void* stream);
+
+/* Outer iterations [first, stop) of the loop for one batch, on the device; no host synchronisation inside the loop.
+ * x_inout: the result; with first > 0 also the iterate entering iteration `first` (with first == 0 the loop starts from x_init).
+ * eps_or_null: (stop - first) * K injected probes [B,C,H,W] each, in the order they are used; NULL = the engine's Rademacher fill, numbered as
+ * pf_flow_priors_params.stream_base says.  Synchronises `stream` and checks the numeric health before returning.
+ * PF_ERR_INVALID with a pf_last_error text (nothing launched): N < 1, K < 1, fd_step <= 0, start_time >= 1, an unknown noise model,
+ * a batch outside 1..65535 (no plan can be built for it), first / stop out of order. */
+int pf_flow_priors_restore(pf_engine* e, const pf_degradation* d, const pf_flow_priors_params* prm, const float* y, const float* x_init,
+                           const float* eps_or_null, float* x_inout, int B, void* stream);
 
 /* Numeric health of the forwards run so far: every GroupNorm finalisation checks the activation statistics it consumes; an
  * overflow / NaN anywhere upstream makes them non-finite and sets a device flag.  This call synchronises `stream`, returns

@@ -141,6 +141,9 @@ def main():
             from pnpflow_amd.methods.pnp_gs import PROX_PNP
             from pnpflow_amd.train_denoiser import GRADIENT_STEP_DENOISER
             method = PROX_PNP(GRADIENT_STEP_DENOISER(model, device, args), device, args)
+        elif args.method == 'flow_priors':
+            from pnpflow_amd.methods.flow_priors import FLOW_PRIORS
+            method = FLOW_PRIORS(model, device, args)
         else:
             raise ValueError("The method your entered does not exist")
         method.run_method(loaders, degradation, sigma_noise)

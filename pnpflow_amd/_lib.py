@@ -70,6 +70,12 @@ class PfPnpGsParams(C.Structure):
                 ("alpha", C.c_double), ("host_cb_mask", C.c_void_p)]
 
 
+class PfFlowPriorsParams(C.Structure):
+    _fields_ = [("N", C.c_int32), ("K", C.c_int32), ("first", C.c_int32), ("stop", C.c_int32), ("lmbda", C.c_double), ("eta", C.c_double),
+                ("start_time", C.c_double), ("fd_step", C.c_double), ("noise_model", C.c_int32), ("reserved0", C.c_int32), ("seed", C.c_uint64),
+                ("stream_base", C.c_uint64), ("time_scale", C.c_double)]
+
+
 ITER_CB = C.CFUNCTYPE(None, C.c_int, C.c_void_p)
 
 # name -> (restype, argtypes); this table is also what tests use to check that every symbol
@@ -128,6 +134,11 @@ SIGNATURES = {
     "pf_gs_denoiser_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pf_pnp_gs_restore": (C.c_int, [C.c_void_p, C.POINTER(PfDegradation), C.POINTER(PfPnpGsParams), C.c_void_p, C.c_void_p, C.POINTER(C.c_double),
                                     C.POINTER(C.c_double), C.c_int, C.c_void_p, ITER_CB, C.c_void_p]),
+    "pf_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p]),
+    "pf_flow_priors_grad": (C.c_int, [C.c_void_p, C.POINTER(PfDegradation), C.POINTER(PfFlowPriorsParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "pf_flow_priors_restore": (C.c_int, [C.c_void_p, C.POINTER(PfDegradation), C.POINTER(PfFlowPriorsParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_int, C.c_void_p]),
     "pf_engine_memory_bytes": (C.c_int64, [C.c_void_p]),
     "pf_engine_check_numerics": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pf_engine_profile": (C.c_int, [C.c_void_p, C.c_int]),

@@ -20,6 +20,7 @@
 #include "pf_common.h"
 #include "weight_pack.h"
 #include "rk45_control.h"
+#include "adam_step.h"
 
 using namespace pf;
 
@@ -130,6 +131,7 @@ struct NxMod {                 // one entry of NCSNpp.all_modules (ncsnpp.py:72-
 
 struct DFlowState;                 // D-Flow / dopri5 buffers and graphs (engine_dflow.inc)
 struct PnpGsState;                 // Prox-PnP (gradient-step denoiser) buffers and graph (engine_pnp_gs.inc)
+struct FlowPriorsState;            // Flow-Priors buffers (engine_flow_priors.inc)
 struct PriorEvalState;             // divergence / Euler sampler / likelihood solve buffers (engine_prior_eval.inc)
 
 struct pf_engine {
@@ -180,6 +182,7 @@ struct pf_engine {
     PnpGsState* pnpgs = nullptr;         // pf_gs_denoiser_grad / pf_pnp_gs_restore state (engine_pnp_gs.inc)
     const void* held_pnpgs_plan = nullptr;   // the plan its cached graph replays (kept out of the eviction as well)
     PriorEvalState* prior = nullptr;     // pf_flow_divergence / pf_flow_ode_euler / pf_flow_likelihood_rk45 state (engine_prior_eval.inc)
+    FlowPriorsState* fprior = nullptr;   // pf_flow_priors_grad / pf_flow_priors_restore state (engine_flow_priors.inc)
     // profiling
     bool profile = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
@@ -1515,6 +1518,7 @@ static void free_dflow(pf_engine* e);
 static void drop_pnpgs_graph(pf_engine* e);
 static void free_pnpgs(pf_engine* e);
 static void free_prior(pf_engine* e);
+static void free_fprior(pf_engine* e);
 int pf_engine_set_solver_time_scale(pf_engine* e, float scale) {
     if (!e || !(scale > 0.f)) return PF_ERR_INVALID;
     if (scale != e->solver_time_scale) { drop_graph(e); drop_ode_graph(e); drop_dflow_graphs(e); drop_pnpgs_graph(e); e->solver_time_scale = scale; }   // the captured graphs bake the scale in
@@ -1572,6 +1576,7 @@ void pf_engine_destroy(pf_engine* e) {
     free_dflow(e);
     free_pnpgs(e);
     free_prior(e);
+    free_fprior(e);
     for (auto& kv : e->plans) for (void* p : kv.second->allocs) hipFree(p);
     for (void* p : e->weight_allocs) hipFree(p);
     for (auto& ev : e->ev_pool) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
@@ -2118,3 +2123,4 @@ int pf_engine_profile_read(pf_engine* e, int64_t* launches, double* ms_conv_gemm
 #include "engine_dflow.inc"
 #include "engine_pnp_gs.inc"
 #include "engine_prior_eval.inc"
+#include "engine_flow_priors.inc"

@@ -325,6 +325,28 @@ hipError_t launch_blur_power_spectrum(const DegView& d, int H, int W, float* pw_
 hipError_t launch_fft_prox_blur(const float* in, const double* alpha_dev, const float* pw_h, const float* pw_w, float* out, int B, int C, int H, int W,
                                 float* cplx, hipStream_t s);
 
+// ---- Flow-Priors glue (flow_priors.hip); flat tensors of any length and alignment ------------------------------------------------
+struct AdamCoef;       // adam_step.h
+struct FlowPriorsCoef {     // scalars of one outer iteration, rounded to fp32 on the host the way torch rounds them
+    float dt;          // fp32(dt)
+    float fd;          // fp32(dt / (2 h)): the central difference and the trace term's dt in one factor
+    float num_t;       // fp32(num_t)
+    float lik;         // fp32(-1 / (1 - num_t))
+    int first;         // outer iteration 0: g_extra = x (the 0.5 sum x^2 term); otherwise grad_xt_lik = lik (num_t pred - x)
+};
+// seed = 2 lmbda r | lmbda sign r (coef = 2 lmbda | lmbda), r = hx - (tn y + omt hxi), over a measurement of n values
+hipError_t launch_fp_seed(const float* hx, const float* y, const float* hxi, float* seed, float tn, float omt, float coef, int laplace, int64_t n, hipStream_t s);
+// identity / box / byte-mask operators: w = H_adj(seed(H(x + pred dt) - y_next)) in one pass
+hipError_t launch_fp_residual(const DegView& d, const float* x, const float* pred, const float* y, const float* hxi, float* w, float dt, float tn, float omt,
+                              float coef, int laplace, int B, int C, int H, int W, hipStream_t s);
+// out = a + c b with the product rounded before the sum (no fma); out may alias a
+hipError_t launch_fp_axpy(const float* a, const float* b, float* out, float c, int64_t n, hipStream_t s);
+hipError_t launch_fp_shift(const float* x, const float* eps, float* xp, float* xm, float h, int64_t n, hipStream_t s);
+// g = (w + dt jw) + fd (jp - jm) + g_extra -> out_* (each may be nullptr); adam != nullptr: the Adam step of x, m, v on g in the same pass
+hipError_t launch_fp_grad_adam(const FlowPriorsCoef& c, const AdamCoef* adam, const float* w, const float* jw, const float* jp, const float* jm, const float* pred,
+                               float* x, float* m, float* v, float* out_g, float* out_g_data, float* out_g_trace, float* out_g_extra, int64_t n, hipStream_t s);
+hipError_t launch_adam_step(const AdamCoef& c, float* x, float* m, float* v, const float* g, int64_t n, hipStream_t s);
+
 // ---- NCSN++ ("rectified") velocity net, the ops that are not convs (ncsnpp_ops.hip) ----------------------------------------
 // FIR resampling of an NHWC activation (upfirdn2d of up_or_down_sampling.py:204-259 on every channel), optionally of TWO views of
 // the same source in one pass: `out_act` takes act(GroupNorm(src)) (the per-image sc/sh of `coef`, SiLU), `out_raw` the raw

@@ -172,7 +172,8 @@ def hut_estimator(NO_test, v, inp, t, eps=None):
 
     The result is a plain VALUE WITHOUT AN AUTOGRAD GRAPH.  The reference builds it with create_graph=True so that Flow-Priors can take
     the trace term's gradient with respect to `inp`; that second-order pass does not exist in this engine, so Flow-Priors cannot be
-    built on this function."""
+    built on this function.  The engine's Flow-Priors (methods/flow_priors.py) takes that gradient from two first-order VJPs instead:
+    pf_flow_priors_grad."""
     net, scale = _velocity_net(v)
     NO_test = int(NO_test)
     if NO_test < 1:
