@@ -138,17 +138,20 @@ typedef enum pf_degradation_kind {
     PF_DEG_MASK_INPAINTING = 2, /* RandomInpainting    degradations.py:35-44 (mask supplied: utils.py:353-361) */
     PF_DEG_SUPERRESOLUTION = 3, /* Superresolution     degradations.py:92-127, mode=None, utils.py:283-310 */
     PF_DEG_GAUSSIAN_BLUR = 4,   /* GaussianDeblurring  degradations.py:55-89 (circular, separable) */
-    PF_DEG_SR_FILTERED = 5      /* Superresolution mode="bicubic": circular separable filter (utils.py:365-396), then decimation
+    PF_DEG_SR_FILTERED = 5,     /* Superresolution mode="bicubic": circular separable filter (utils.py:365-396), then decimation
                                    degradations.py:97-127; uses sf, ntaps (4*sf, even), taps */
+    PF_DEG_GAUSSIAN_BLUR_ZERO = 6 /* GaussianDeblurring, any mode but "fft" (degradations.py:72-76, 82-86): F.conv2d(padding='same'), i.e. the
+                                   correlation with outer(taps, taps) where samples outside the image are 0; H_adj is the matching convolution
+                                   (= H for the symmetric Gaussian).  Same fields as GAUSSIAN_BLUR (ntaps, taps); no ntaps < H restriction */
 } pf_degradation_kind;
 
 typedef struct pf_degradation {
     int32_t kind;
     int32_t half_size_mask;     /* BOX */
     int32_t sf;                 /* SUPERRESOLUTION */
-    int32_t ntaps;              /* GAUSSIAN_BLUR / SR_FILTERED: <= 127; tap ntaps/2 sits at offset 0 (the reference's roll by -(K-1)//2) */
+    int32_t ntaps;              /* GAUSSIAN_BLUR / GAUSSIAN_BLUR_ZERO / SR_FILTERED: <= 127; tap ntaps/2 sits at offset 0 (the reference's roll by -(K-1)//2) */
     const uint8_t* mask;        /* MASK: device [B][H][W] bytes, 1 = keep */
-    const float* taps;          /* GAUSSIAN_BLUR: device [ntaps] separable 1-D taps */
+    const float* taps;          /* GAUSSIAN_BLUR / GAUSSIAN_BLUR_ZERO / SR_FILTERED: device [ntaps] separable 1-D taps */
 } pf_degradation;
 
 /* y = H(x)      x:[B,C,H,W] -> y:[B,C,Hy,Wy]  (Hy = H/sf for SR, else H) */
@@ -161,7 +164,7 @@ int pf_degradation_H_adj(const pf_degradation* d, const float* y, float* x, int 
 /* ---- PnP-Flow iteration pieces (pnpflow/methods/pnp_flow.py) ------------------------- */
 /* z = x - coef[b] * H_adj(H(x) - y),  coef[b] = lr_t[b] / sigma^2
  * replaces grad_datafit + the update at pnp_flow.py:39-41, 109-112 (gaussian noise).
- * scratch: >= 2*B*C*H*W floats for GAUSSIAN_BLUR and SR_FILTERED (pf_degradation_H/H_adj: B*C*H*W resp. 2*B*C*H*W), may be NULL otherwise. */
+ * scratch: >= 2*B*C*H*W floats for GAUSSIAN_BLUR, GAUSSIAN_BLUR_ZERO and SR_FILTERED (pf_degradation_H/H_adj: B*C*H*W resp. 2*B*C*H*W), may be NULL otherwise. */
 int pf_grad_step(const pf_degradation* d, const float* x, const float* y, const float* coef, float* z,
                  int B, int C, int H, int W, float* scratch, void* stream);
 /* Laplace noise model (pnp_flow.py:42-43): z = x - coef[b] * H_adj(2*heaviside(H(x) - y, 0) - 1), coef[b] = lr_t[b]/sigma */
@@ -250,13 +253,30 @@ int pf_ot_ode_vec(const pf_degradation* d, const float* x, const float* vt, cons
 int pf_ot_ode_update(float* x, const float* vt, const float* vec, const float* g, const float* one_minus_t,
                      const float* coef, float delta, int B, int n_per_image, void* stream);
 
+/* Batched GMRES on the device (the reference's utils.GMRES, pnpflow/utils.py:972-1109, as ot_ode.py:119-128 calls it), all images at once:
+ *   (rt2[b] H H^T + sigma2 I) sol[b] = rhs[b]
+ * from a zero initial guess, at most max_iter (<= 256) Krylov vectors, no restart; image b stops when |beta_{j+1}| < tol |rhs_b| or < atol;
+ * |rhs_b| < 1e-8 returns rhs_b itself (utils.py:995-996).  Orthogonalisation: classical Gram-Schmidt with one re-orthogonalisation pass (two
+ * multi-dot + update launch pairs per iteration); Hessenberg column, Givens rotations, beta and the per-image done flag stay on the device,
+ * the host only polls the flags every 8 iterations to leave early (never under stream capture: max_iter masked iterations then).  Reductions
+ * have a fixed order: two runs agree bit for bit.  Every kind whose measurement has the image's shape; the superresolution kinds return
+ * PF_ERR_INVALID.  rt2_dev: device [B]; rhs, sol: device [B,C,H,W] (distinct); workspace: device, 16-byte aligned, workspace_floats >=
+ * pf_krylov_workspace_floats(...) = (max_iter + 3) B C H W floats (basis + two operator temporaries) + the small per-image state;
+ * iters_out_dev: device int32 [B] or NULL <- Krylov vectors in image b's solution (0 for the |rhs_b| < 1e-8 return). */
+int64_t pf_krylov_workspace_floats(int B, int C, int H, int W, int max_iter);
+int pf_krylov_solve(const pf_degradation* d, const float* rt2_dev, float sigma2, const float* rhs, float* sol, int B, int C, int H, int W,
+                    int max_iter, float tol, float atol, float* workspace, int64_t workspace_floats, int32_t* iters_out_dev, void* stream);
+
 /* Whole OT-ODE loop of one batch on the device (pnpflow/methods/ot_ode.py:63-147): iterations first..steps-1 of
  *   v_t = v_theta(x, t);  vec = H_adj((r_t^2 H H^T + sigma^2)^-1 (y - H(x + (1-t) v_t)));  g = J^T vec;
  *   x += delta * (v_t + coef * (vec + (1-t) g))
  * with the per-iteration scalars (host tables, fp32 values computed with the reference's own expressions - including its
  * `delta * iteration**2` quirk for superresolution, ot_ode.py:96) read on the device through an iteration counter, the buffers
  * pre-allocated, and one hipGraph per Euler step (retained forward -> solve -> hand-written backward -> update) captured once
- * and replayed.  x_inout: the initialisation t0*H_adj(y) + (1-t0)*noise on entry (ot_ode.py:27-28, 50-52), the result on exit. */
+ * and replayed.  GAUSSIAN_BLUR_ZERO has no closed form: its step is the reference's generic branch (ot_ode.py:119-128) - retained forward,
+ * d = y - H(x + (1-t) v_t), pf_krylov_solve (max_iter 100, tol = atol = 1e-6), vec = H_adj(sol), backward, update - as two captured halves with
+ * the Krylov loop enqueued between them; pf_ot_ode_krylov_iterations reports how many Krylov iterations the last call enqueued.
+ * x_inout: the initialisation t0*H_adj(y) + (1-t0)*noise on entry (ot_ode.py:27-28, 50-52), the result on exit. */
 typedef struct pf_ot_ode_params {
     int32_t steps;                  /* steps_ode */
     int32_t first;                  /* int(steps_ode * start_time) */
@@ -272,6 +292,8 @@ typedef struct pf_ot_ode_params {
 } pf_ot_ode_params;
 int pf_ot_ode_restore(pf_engine* e, const pf_degradation* d, const pf_ot_ode_params* prm, const float* y, float* x_inout, int B,
                       void* stream, void (*iter_cb)(int iteration, void* user), void* user);
+/* Krylov iterations enqueued by the engine loop of the last pf_ot_ode_restore (0 when its operator has a closed-form solve) */
+int64_t pf_ot_ode_krylov_iterations(const pf_engine* e);
 
 /* ---- D-Flow (pnpflow/methods/d_flow.py) ------------------------------------------------------------------------------------
  * T(z) = steps_euler - 1 explicit midpoint steps of the velocity net (forward_flow_matching, d_flow.py:41-49):

@@ -56,6 +56,8 @@ def make_degradation(problem, dim_image, num_channels, noise_type, device):
         return D.Superresolution({128: 2, 256: 4}[dim_image], dim_image), (0.3 if lap else 0.05)
     if problem == "gaussian_deblurring_FFT":
         return D.GaussianDeblurring({128: 1.0, 256: 3.0}[dim_image], 61, "fft", num_channels, dim_image, device), (0.3 if lap else 0.05)
+    if problem == "gaussian_deblurring":      # the same blur with a zero boundary (degradations.py:72-76: any mode but "fft" is F.conv2d(padding='same'))
+        return D.GaussianDeblurring({128: 1.0, 256: 3.0}[dim_image], 61, "spatial", num_channels, dim_image, device), (0.3 if lap else 0.05)
     raise ValueError("The problem you entered is not implemented by this engine: " + str(problem))
 
 

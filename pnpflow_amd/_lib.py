@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("PNPFLOW_HIP_LIB") or os.path.join(_HERE, "libpnpflow_
 PF_ABI_VERSION = 6
 
 PF_DEG_DENOISING, PF_DEG_BOX_INPAINTING, PF_DEG_MASK_INPAINTING, PF_DEG_SUPERRESOLUTION, PF_DEG_GAUSSIAN_BLUR, PF_DEG_SR_FILTERED = range(6)
+PF_DEG_GAUSSIAN_BLUR_ZERO = 6      # zero-boundary Gaussian blur (GaussianDeblurring, any mode but "fft")
 
 
 class PfUnetCfg(C.Structure):
@@ -122,6 +123,10 @@ SIGNATURES = {
     "pf_lpips_load_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
     "pf_lpips_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "pf_ot_ode_restore": (C.c_int, [C.c_void_p, C.POINTER(PfDegradation), C.POINTER(PfOtOdeParams), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, ITER_CB, C.c_void_p]),
+    "pf_ot_ode_krylov_iterations": (C.c_int64, [C.c_void_p]),
+    "pf_krylov_workspace_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "pf_krylov_solve": (C.c_int, [C.POINTER(PfDegradation), C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                  C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "pf_pnp_flow_restore": (C.c_int, [C.c_void_p, C.POINTER(PfDegradation), C.POINTER(PfPnpParams), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, ITER_CB, C.c_void_p]),
     "pf_d_flow_forward": (C.c_int, [C.c_void_p, C.POINTER(PfDFlowParams), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pf_d_flow_value_and_grad": (C.c_int, [C.c_void_p, C.POINTER(PfDegradation), C.POINTER(PfDFlowParams), C.c_void_p, C.c_void_p, C.c_float,

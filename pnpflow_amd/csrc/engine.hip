@@ -171,11 +171,14 @@ struct pf_engine {
                          // 2: single fp16 MFMA per product (fp16 operands, fp32 accumulate - TF32-class, include/pnpflow_hip.h)
     SolverBufs sb;
     // OT-ODE loop (pf_ot_ode_restore): iterate, velocity, solve output, J^T vec, per-iteration schedule tables, cached graph
-    struct OdeBufs { int B = 0; size_t n = 0, ny = 0; int steps = 0; bool blur = false;
+    struct OdeBufs { int B = 0; size_t n = 0, ny = 0; int steps = 0; int solve = 0 /* 0 closed form, 1 Fourier (circular blur), 2 Krylov (zero-boundary blur) */;
                      float *x = nullptr, *vt = nullptr, *vec = nullptr, *g = nullptr, *y = nullptr, *scratch = nullptr;
+                     float *dres = nullptr, *sol = nullptr, *kry = nullptr /* Krylov right-hand side, solution, workspace */; size_t kry_floats = 0;
                      float *tab = nullptr /* [4][steps]: t, 1-t, r_t^2, coef */, *cur = nullptr /* [4][B] */; int* iter = nullptr; int64_t bytes = 0; } ob;
     struct OdeKey { const void* plan; int kind, half, sf, ntaps; const void* mask; const void* taps; int B; float sigma2, delta; int pad_; };   // compared with memcmp: no implicit padding (static_assert below)
     OdeKey okey{}; hipGraph_t ograph = nullptr; hipGraphExec_t ogexec = nullptr;
+    hipGraph_t ograph2 = nullptr; hipGraphExec_t ogexec2 = nullptr;      // Krylov solve: the step is two captured halves (ograph: up to d, ograph2: from H_adj(sol)) with the Krylov loop between them
+    int64_t ode_krylov_iters = 0;        // Krylov iterations enqueued by the last pf_ot_ode_restore
     hipStream_t work_stream = nullptr;   // used when the caller passes the NULL stream and asks for graph replay
     DFlowState* dflow = nullptr;         // pf_d_flow_* / pf_flow_ode_dopri5 state (engine_dflow.inc)
     const void* held_plans[3] = {};      // plans a cached D-Flow graph replays (kept out of the plan cache's eviction)
@@ -1962,31 +1965,53 @@ __global__ void ode_prep_kernel(const int* iter, const float* tab, int steps, fl
 static void drop_ode_graph(pf_engine* e) {
     if (e->ogexec) hipGraphExecDestroy(e->ogexec);
     if (e->ograph) hipGraphDestroy(e->ograph);
-    e->ogexec = nullptr; e->ograph = nullptr; e->okey = pf_engine::OdeKey{};
+    if (e->ogexec2) hipGraphExecDestroy(e->ogexec2);
+    if (e->ograph2) hipGraphDestroy(e->ograph2);
+    e->ogexec = nullptr; e->ograph = nullptr; e->ogexec2 = nullptr; e->ograph2 = nullptr; e->okey = pf_engine::OdeKey{};
 }
 
 static void free_ode(pf_engine* e) {
     drop_ode_graph(e);
     auto& b = e->ob;
-    for (void* p : {(void*)b.x, (void*)b.vt, (void*)b.vec, (void*)b.g, (void*)b.y, (void*)b.scratch, (void*)b.tab, (void*)b.cur, (void*)b.iter})
+    for (void* p : {(void*)b.x, (void*)b.vt, (void*)b.vec, (void*)b.g, (void*)b.y, (void*)b.scratch, (void*)b.tab, (void*)b.cur, (void*)b.iter, (void*)b.dres, (void*)b.sol, (void*)b.kry})
         if (p) hipFree(p);
     e->bytes -= b.bytes;
     b = pf_engine::OdeBufs{};
 }
 
-static int ensure_ode(pf_engine* e, int B, size_t n, size_t ny, int steps, bool blur, int H) {
+constexpr int ODE_KRYLOV_MAX_ITER = 100;       // utils.GMRES(C_ope, d, max_iter=100), ot_ode.py:126-127; tol = atol = 1e-6 are its defaults
+
+static int ensure_ode(pf_engine* e, int B, size_t n, size_t ny, int steps, int solve, int H) {
     auto& b = e->ob;
-    if (b.B == B && b.n == n && b.ny == ny && b.steps >= steps && b.blur == blur) return PF_OK;
+    if (b.B == B && b.n == n && b.ny == ny && b.steps >= steps && b.solve == solve) return PF_OK;
     free_ode(e);
     const size_t tot = (size_t)B * n;
     HIPCHK(e, hipMalloc(&b.x, tot * 4)); HIPCHK(e, hipMalloc(&b.vt, tot * 4)); HIPCHK(e, hipMalloc(&b.vec, tot * 4)); HIPCHK(e, hipMalloc(&b.g, tot * 4));
     HIPCHK(e, hipMalloc(&b.y, (size_t)B * ny * 4));
-    const size_t scr = blur ? 4 * tot + 2 * (size_t)H : 0;
+    const size_t scr = solve == 1 ? 4 * tot + 2 * (size_t)H : solve == 2 ? tot : 0;
     if (scr) HIPCHK(e, hipMalloc(&b.scratch, scr * 4));
+    size_t kry_bytes = 0;
+    if (solve == 2) {
+        HIPCHK(e, hipMalloc(&b.dres, tot * 4)); HIPCHK(e, hipMalloc(&b.sol, tot * 4));
+        b.kry_floats = krylov_workspace_floats(B, n, ODE_KRYLOV_MAX_ITER);
+        const hipError_t ke = hipMalloc(&b.kry, b.kry_floats * 4);
+        if (ke != hipSuccess) {
+            (void)hipGetLastError();
+            b.kry = nullptr;
+            const size_t want = b.kry_floats * 4;
+            b.B = 0; b.bytes = 0;        // (nothing is accounted yet: free_ode releases what was allocated)
+            free_ode(e);
+            e->err = "ot_ode: cannot allocate the Krylov workspace of " + std::to_string(want) + " bytes (" + std::to_string(ODE_KRYLOV_MAX_ITER + 3) +
+                     " x batch x image floats): " + hipGetErrorString(ke);
+            return PF_ERR_HIP;
+        }
+        kry_bytes = 2 * tot * 4 + b.kry_floats * 4;
+        if (poison_enabled()) { poison(b.dres, tot * 4, 4); poison(b.sol, tot * 4, 4); poison(b.kry, b.kry_floats * 4, 4); }
+    }
     HIPCHK(e, hipMalloc(&b.tab, (size_t)4 * steps * 4)); HIPCHK(e, hipMalloc(&b.cur, (size_t)4 * B * 4)); HIPCHK(e, hipMalloc(&b.iter, 64));
     if (poison_enabled()) { for (float* q : {b.x, b.vt, b.vec, b.g}) poison(q, tot * 4, 4); poison(b.y, (size_t)B * ny * 4, 4); poison(b.scratch, scr * 4, 4); poison(b.tab, (size_t)4 * steps * 4, 4); poison(b.cur, (size_t)4 * B * 4, 4); }
-    b.B = B; b.n = n; b.ny = ny; b.steps = steps; b.blur = blur;
-    b.bytes = (int64_t)(4 * tot * 4 + (size_t)B * ny * 4 + scr * 4 + (size_t)4 * steps * 4 + (size_t)4 * B * 4 + 64);
+    b.B = B; b.n = n; b.ny = ny; b.steps = steps; b.solve = solve;
+    b.bytes = (int64_t)(4 * tot * 4 + (size_t)B * ny * 4 + scr * 4 + kry_bytes + (size_t)4 * steps * 4 + (size_t)4 * B * 4 + 64);
     e->bytes += b.bytes;
     return PF_OK;
 }
@@ -2013,6 +2038,71 @@ static int enqueue_ode_step(pf_engine* e, Plan* plan, const DegView& dv, const p
     return PF_OK;
 }
 
+// The generic branch (ot_ode.py:119-128; the zero-boundary blur has no closed-form solve) as two halves around the Krylov loop:
+// half A  v_t = v_theta(x, t), d = y - H(x + (1-t) v_t);   [launch_krylov_solve: sol = (r_t^2 H H^T + sigma^2)^-1 d];   half B  vec = H_adj(sol),
+// g = J^T vec, update.  Each half is capturable on its own; the loop between them polls its done flags and therefore is not.
+static int enqueue_ode_krylov_a(pf_engine* e, Plan* plan, const DegView& dv, int B, int C, int H, hipStream_t s) {
+    auto& b = e->ob;
+    const int n = C * H * H;
+    hipLaunchKernelGGL(ode_prep_kernel, dim3(1), dim3(256), 0, s, (const int*)b.iter, (const float*)b.tab, b.steps, b.cur, B);
+    const float* t_cur = b.cur; const float* omt = b.cur + B;
+    int rc = run_plan(e, plan, b.x, t_cur, b.vt, s, e->solver_time_scale);
+    if (rc != PF_OK) return rc;
+    hipError_t r = launch_ot_ode_x1hat(b.x, b.vt, omt, b.g, B, n, s);                        // x1_hat (b.g is free until the backward)
+    if (r == hipSuccess) r = launch_deg_H(dv, b.g, b.vec, B, C, H, H, b.scratch, s);
+    if (r == hipSuccess) r = launch_ot_ode_residual(b.y, b.vec, b.dres, B, n, s);
+    if (r != hipSuccess) { e->err = std::string("ot_ode residual: ") + hipGetErrorString(r); return PF_ERR_HIP; }
+    return PF_OK;
+}
+
+static int enqueue_ode_krylov_b(pf_engine* e, Plan* plan, const DegView& dv, const pf_ot_ode_params* prm, int B, int C, int H, hipStream_t s) {
+    auto& b = e->ob;
+    const int n = C * H * H;
+    const float* omt = b.cur + B; const float* coef = b.cur + 3 * B;
+    hipError_t r = launch_deg_Hadj(dv, b.sol, b.vec, B, C, H, H, b.scratch, s);
+    if (r != hipSuccess) { e->err = std::string("ot_ode H_adj: ") + hipGetErrorString(r); return PF_ERR_HIP; }
+    int rc = run_backward(e, plan, b.vec, b.g, s);
+    if (rc != PF_OK) return rc;
+    r = launch_ot_ode_update(b.x, b.vt, b.vec, b.g, omt, coef, prm->delta, B, n, s);
+    if (r != hipSuccess) { e->err = std::string("ot_ode update: ") + hipGetErrorString(r); return PF_ERR_HIP; }
+    hipLaunchKernelGGL(bump_iter_kernel, dim3(1), dim3(64), 0, s, b.iter);
+    r = hipGetLastError();
+    if (r != hipSuccess) { e->err = std::string("ot_ode step: ") + hipGetErrorString(r); return PF_ERR_HIP; }
+    return PF_OK;
+}
+
+// captures fn() on s into *graph / *exec
+static int capture_ode_half(pf_engine* e, hipStream_t s, hipGraph_t* graph, hipGraphExec_t* exec, const std::function<int()>& fn) {
+    HIPCHK(e, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    const int rc = fn();
+    hipGraph_t g = nullptr;
+    const hipError_t ce = hipStreamEndCapture(s, &g);
+    if (rc != PF_OK) { if (g) hipGraphDestroy(g); return rc; }
+    if (ce != hipSuccess) { e->err = std::string("hipStreamEndCapture: ") + hipGetErrorString(ce); return PF_ERR_HIP; }
+    *graph = g;
+    const hipError_t ie = hipGraphInstantiate(exec, g, nullptr, nullptr, 0);
+    if (ie != hipSuccess) { drop_ode_graph(e); e->err = std::string("hipGraphInstantiate: ") + hipGetErrorString(ie); return PF_ERR_HIP; }
+    return PF_OK;
+}
+
+int64_t pf_ot_ode_krylov_iterations(const pf_engine* e) { return e ? e->ode_krylov_iters : 0; }
+
+int64_t pf_krylov_workspace_floats(int B, int C, int H, int W, int max_iter) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || max_iter < 0) return 0;
+    return (int64_t)krylov_workspace_floats(B, (size_t)C * H * W, max_iter);
+}
+
+int pf_krylov_solve(const pf_degradation* d, const float* rt2_dev, float sigma2, const float* rhs, float* sol, int B, int C, int H, int W, int max_iter,
+                    float tol, float atol, float* workspace, int64_t workspace_floats, int32_t* iters_out_dev, void* stream) {
+    if (!d || !rt2_dev || !rhs || !sol || rhs == sol || !workspace || workspace_floats <= 0) return PF_ERR_INVALID;
+    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_GAUSSIAN_BLUR_ZERO || d->kind == PF_DEG_SUPERRESOLUTION || d->kind == PF_DEG_SR_FILTERED) return PF_ERR_INVALID;
+    if ((d->kind == PF_DEG_GAUSSIAN_BLUR || d->kind == PF_DEG_GAUSSIAN_BLUR_ZERO) && (!d->taps || d->ntaps < 1 || d->ntaps > 127)) return PF_ERR_INVALID;
+    if (d->kind == PF_DEG_MASK_INPAINTING && !d->mask) return PF_ERR_INVALID;
+    LAUNCHCHK(launch_krylov_solve(to_view(d), rt2_dev, sigma2, rhs, sol, B, C, H, W, max_iter, tol, atol, workspace, (size_t)workspace_floats, iters_out_dev,
+                                  (hipStream_t)stream));
+    return PF_OK;
+}
+
 int pf_ot_ode_restore(pf_engine* e, const pf_degradation* d, const pf_ot_ode_params* prm, const float* y, float* x_inout, int B,
                       void* stream, pf_iter_callback iter_cb, void* user) {
     if (!e || !d || !prm || !y || !x_inout || B <= 0 || prm->steps <= 0 || prm->first < 0 || prm->first > prm->steps || !prm->host_t ||
@@ -2032,7 +2122,11 @@ int pf_ot_ode_restore(pf_engine* e, const pf_degradation* d, const pf_ot_ode_par
     const size_t n = (size_t)C * H * H;
     const int Hy = d->kind == PF_DEG_SUPERRESOLUTION ? H / std::max(1, d->sf) : H;
     const size_t ny = (size_t)C * Hy * Hy;
-    int rc = ensure_ode(e, B, n, ny, prm->steps, d->kind == PF_DEG_GAUSSIAN_BLUR, H);
+    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_GAUSSIAN_BLUR_ZERO) { e->err = "ot_ode: unknown degradation kind"; return PF_ERR_INVALID; }
+    const bool krylov = d->kind == PF_DEG_GAUSSIAN_BLUR_ZERO;
+    if (krylov && (!d->taps || d->ntaps < 1 || d->ntaps > 127)) { e->err = "ot_ode: the zero-boundary blur needs 1 .. 127 device taps"; return PF_ERR_INVALID; }
+    e->ode_krylov_iters = 0;
+    int rc = ensure_ode(e, B, n, ny, prm->steps, krylov ? 2 : d->kind == PF_DEG_GAUSSIAN_BLUR ? 1 : 0, H);
     if (rc != PF_OK) return rc;
     auto& b = e->ob;
     Plan* plan = nullptr;
@@ -2056,7 +2150,23 @@ int pf_ot_ode_restore(pf_engine* e, const pf_degradation* d, const pf_ot_ode_par
     if (e->ogexec && memcmp(&key, &e->okey, sizeof key) != 0) drop_ode_graph(e);
     const bool can_graph = prm->use_graph && !e->profile;
     for (int it = first; it < prm->steps; ++it) {
-        if (can_graph && (it > first || e->ogexec)) {
+        if (krylov) {
+            const bool replay = can_graph && (it > first || e->ogexec);
+            if (replay && !e->ogexec) {
+                if ((rc = capture_ode_half(e, s, &e->ograph, &e->ogexec, [&] { return enqueue_ode_krylov_a(e, plan, dv, B, C, H, s); })) != PF_OK) { drop_ode_graph(e); return rc; }
+                if ((rc = capture_ode_half(e, s, &e->ograph2, &e->ogexec2, [&] { return enqueue_ode_krylov_b(e, plan, dv, prm, B, C, H, s); })) != PF_OK) { drop_ode_graph(e); return rc; }
+                memset(&e->okey, 0, sizeof e->okey); e->okey = key;
+            }
+            if (replay) HIPCHK(e, hipGraphLaunch(e->ogexec, s));
+            else if ((rc = enqueue_ode_krylov_a(e, plan, dv, B, C, H, s)) != PF_OK) return rc;
+            int ran = 0;
+            const hipError_t kr = launch_krylov_solve(dv, b.cur + 2 * B, prm->sigma2, b.dres, b.sol, B, C, H, H, ODE_KRYLOV_MAX_ITER, 1e-6f, 1e-6f, b.kry, b.kry_floats,
+                                                     nullptr, s, &ran);
+            if (kr != hipSuccess) { e->err = std::string("ot_ode Krylov solve: ") + hipGetErrorString(kr); return PF_ERR_HIP; }
+            e->ode_krylov_iters += ran;
+            if (replay) HIPCHK(e, hipGraphLaunch(e->ogexec2, s));
+            else if ((rc = enqueue_ode_krylov_b(e, plan, dv, prm, B, C, H, s)) != PF_OK) return rc;
+        } else if (can_graph && (it > first || e->ogexec)) {
             if (!e->ogexec) {
                 HIPCHK(e, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
                 rc = enqueue_ode_step(e, plan, dv, prm, B, C, H, s);

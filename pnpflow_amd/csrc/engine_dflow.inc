@@ -257,10 +257,10 @@ int pf_d_flow_value_and_grad(pf_engine* e, const pf_degradation* d, const pf_d_f
     if (rc != PF_OK) return rc;
     const int C = e->cfg.input_channels, H = e->cfg.input_height;
     const size_t n = (size_t)C * H * H;
-    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_SR_FILTERED) { e->err = "d_flow: unknown degradation kind"; return PF_ERR_INVALID; }
+    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_GAUSSIAN_BLUR_ZERO) { e->err = "d_flow: unknown degradation kind"; return PF_ERR_INVALID; }
     const bool sr = d->kind == PF_DEG_SUPERRESOLUTION || d->kind == PF_DEG_SR_FILTERED;
     if (sr && (d->sf <= 0 || H % d->sf)) { e->err = "d_flow: superresolution factor must divide the image size"; return PF_ERR_INVALID; }
-    if ((d->kind == PF_DEG_GAUSSIAN_BLUR || d->kind == PF_DEG_SR_FILTERED) && (!d->taps || d->ntaps < 1 || d->ntaps > 127)) {
+    if ((d->kind == PF_DEG_GAUSSIAN_BLUR || d->kind == PF_DEG_GAUSSIAN_BLUR_ZERO || d->kind == PF_DEG_SR_FILTERED) && (!d->taps || d->ntaps < 1 || d->ntaps > 127)) {
         e->err = "d_flow: the filtered operators need 1..127 device taps"; return PF_ERR_INVALID;
     }
     if (d->kind == PF_DEG_MASK_INPAINTING && !d->mask) { e->err = "d_flow: mask inpainting needs a device mask"; return PF_ERR_INVALID; }

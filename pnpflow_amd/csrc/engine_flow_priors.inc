@@ -115,11 +115,11 @@ static int fp_begin(pf_engine* e, const pf_degradation* d, const pf_flow_priors_
     if (!(prm->lmbda >= 0.0) || !(prm->eta >= 0.0)) { e->err = "flow_priors: lmbda and eta must not be negative"; return PF_ERR_INVALID; }
     // a plan is built per batch size on first use; what no plan can be built for is refused here, before anything is allocated
     if (B < 1 || B > 65535) { e->err = "flow_priors: batch " + std::to_string(B) + " is not one the engine plans for (1..65535 images)"; return PF_ERR_INVALID; }
-    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_SR_FILTERED) { e->err = "flow_priors: unknown degradation kind"; return PF_ERR_INVALID; }
+    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_GAUSSIAN_BLUR_ZERO) { e->err = "flow_priors: unknown degradation kind"; return PF_ERR_INVALID; }
     const int C = e->cfg.input_channels, H = e->cfg.input_height;
     const bool sr = d->kind == PF_DEG_SUPERRESOLUTION || d->kind == PF_DEG_SR_FILTERED;
     if (sr && (d->sf <= 0 || H % d->sf)) { e->err = "flow_priors: superresolution factor must divide the image size"; return PF_ERR_INVALID; }
-    if ((d->kind == PF_DEG_GAUSSIAN_BLUR || d->kind == PF_DEG_SR_FILTERED) && (!d->taps || d->ntaps < 1 || d->ntaps > 127)) {
+    if ((d->kind == PF_DEG_GAUSSIAN_BLUR || d->kind == PF_DEG_GAUSSIAN_BLUR_ZERO || d->kind == PF_DEG_SR_FILTERED) && (!d->taps || d->ntaps < 1 || d->ntaps > 127)) {
         e->err = "flow_priors: the filtered operators need 1..127 device taps"; return PF_ERR_INVALID;
     }
     if (d->kind == PF_DEG_MASK_INPAINTING && !d->mask) { e->err = "flow_priors: mask inpainting needs a device mask"; return PF_ERR_INVALID; }

@@ -166,6 +166,10 @@ int pf_pnp_gs_restore(pf_engine* e, const pf_degradation* d, const pf_pnp_gs_par
     if (e->cfg.output_channels != e->cfg.input_channels) { e->err = "pnp_gs needs output_channels == input_channels"; return PF_ERR_INVALID; }
     if (prm->algo < 0 || prm->algo > 2) { e->err = "pnp_gs: algo must be 0 (pgd), 1 (hqs random_inpainting) or 2 (hqs gaussian_deblurring_FFT)"; return PF_ERR_INVALID; }
     if (prm->algo == 1 && (d->kind != PF_DEG_MASK_INPAINTING || !d->mask)) { e->err = "pnp_gs: algo 1 (hqs random_inpainting) needs a PF_DEG_MASK_INPAINTING operator with a device mask"; return PF_ERR_INVALID; }
+    if (prm->algo == 2 && d->kind == PF_DEG_GAUSSIAN_BLUR_ZERO) {
+        e->err = "pnp_gs: algo 2 (hqs) has no zero-boundary form: its prox is a Fourier solve of the CIRCULAR blur (PF_DEG_GAUSSIAN_BLUR); use algo 0 (pgd) with PF_DEG_GAUSSIAN_BLUR_ZERO";
+        return PF_ERR_INVALID;
+    }
     if (prm->algo == 2 && d->kind != PF_DEG_GAUSSIAN_BLUR) { e->err = "pnp_gs: algo 2 (hqs gaussian_deblurring_FFT) needs a PF_DEG_GAUSSIAN_BLUR operator"; return PF_ERR_INVALID; }
     if (prm->noise_model != 0 && prm->noise_model != 1) { e->err = "pnp_gs: noise_model must be 0 (gaussian) or 1 (laplace)"; return PF_ERR_INVALID; }
     if (prm->noise_model == 1 && prm->algo != 0) { e->err = "pnp_gs: the laplace noise model exists for algo 0 (pgd) only"; return PF_ERR_INVALID; }
@@ -174,12 +178,15 @@ int pf_pnp_gs_restore(pf_engine* e, const pf_degradation* d, const pf_pnp_gs_par
     }
     if (!prm->host_sigma_den) { e->err = "pnp_gs: host_sigma_den (the denoiser level of every iteration) is required"; return PF_ERR_INVALID; }
     if (!(prm->alpha > 0.0)) { e->err = "pnp_gs: alpha must be positive"; return PF_ERR_INVALID; }
-    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_SR_FILTERED) { e->err = "pnp_gs: unknown degradation kind"; return PF_ERR_INVALID; }
+    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_GAUSSIAN_BLUR_ZERO) { e->err = "pnp_gs: unknown degradation kind"; return PF_ERR_INVALID; }
     const int C = e->cfg.input_channels, H = e->cfg.input_height;
     const bool sr = d->kind == PF_DEG_SUPERRESOLUTION || d->kind == PF_DEG_SR_FILTERED;
     if (sr && (d->sf <= 0 || H % d->sf)) { e->err = "pnp_gs: superresolution factor must divide the image size"; return PF_ERR_INVALID; }
     if ((d->kind == PF_DEG_GAUSSIAN_BLUR || d->kind == PF_DEG_SR_FILTERED) && (!d->taps || d->ntaps < 1 || d->ntaps > 127 || d->ntaps > H)) {
         e->err = "pnp_gs: the filtered operators need 1..127 device taps (at most the image size)"; return PF_ERR_INVALID;
+    }
+    if (d->kind == PF_DEG_GAUSSIAN_BLUR_ZERO && (!d->taps || d->ntaps < 1 || d->ntaps > 127)) {
+        e->err = "pnp_gs: the zero-boundary blur needs 1..127 device taps"; return PF_ERR_INVALID;
     }
     if (d->kind == PF_DEG_MASK_INPAINTING && !d->mask) { e->err = "pnp_gs: mask inpainting needs a device mask"; return PF_ERR_INVALID; }
     const int Hy = sr ? H / d->sf : H;

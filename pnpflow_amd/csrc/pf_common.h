@@ -239,7 +239,7 @@ hipError_t launch_softmax_bwd(const float* A, float* dA, int64_t rows, int cols,
 hipError_t launch_sumpool2(const float* in, float* out, int B, int H, int W, int C, int accumulate, hipStream_t s);
 
 // pointwise / operator kernels (NCHW fp32 images)
-enum { DEG_DENOISE = 0, DEG_BOX = 1, DEG_MASK = 2, DEG_SR = 3, DEG_BLUR = 4, DEG_SR_FILTER = 5 };
+enum { DEG_DENOISE = 0, DEG_BOX = 1, DEG_MASK = 2, DEG_SR = 3, DEG_BLUR = 4, DEG_SR_FILTER = 5, DEG_BLUR_ZERO = 6 /* same taps, samples outside the image are 0 */ };
 struct DegView {       // device-side view of pf_degradation
     int kind, half, sf, ntaps;
     const uint8_t* mask;
@@ -276,6 +276,16 @@ hipError_t launch_ot_ode_vec_blur(const DegView& d, const float* x, const float*
                                   const float* rt2, float sigma2, float* vec, int B, int C, int H, int W, float* scratch, hipStream_t s);
 hipError_t launch_ot_ode_update(float* x, const float* vt, const float* vec, const float* g, const float* one_minus_t, const float* coef,
                                 float delta, int B, int n, hipStream_t s);
+
+// generic branch (no closed-form solve): x1 = x + (1-t) v;  d = y - hx;  then the batched GMRES of krylov.hip
+hipError_t launch_ot_ode_x1hat(const float* x, const float* vt, const float* one_minus_t, float* x1, int B, int n, hipStream_t s);
+hipError_t launch_ot_ode_residual(const float* y, const float* hx, float* d, int B, int n, hipStream_t s);
+// (rt2[b] H H^T + sigma2 I) sol[b] = rhs[b] by GMRES from 0, all images at once, no host round trip per iteration (krylov.hip); every kind whose
+// measurement has the image's shape.  ws: krylov_workspace_floats(B, C*H*W, max_iter) floats, 16-byte aligned; iters_out (device, or nullptr)
+// <- Krylov vectors in each image's solution (0: |rhs| < 1e-8, sol = rhs); iterations_run (host, or nullptr) <- iterations enqueued
+size_t krylov_workspace_floats(int B, size_t n, int max_iter);
+hipError_t launch_krylov_solve(const DegView& d, const float* rt2, float sigma2, const float* rhs, float* sol, int B, int C, int H, int W, int max_iter,
+                               float tol, float atol, float* ws, size_t ws_floats, int* iters_out, hipStream_t s, int* iterations_run = nullptr);
 
 // ---- D-Flow and dopri5 glue (flow_solvers.hip) --------------------------------------------------------------------------------
 struct RkTerms { const float* k[7]; float c[7]; int n; };     // sum_j c[j] * k[j], j < n

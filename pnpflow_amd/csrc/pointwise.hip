@@ -128,6 +128,8 @@ __global__ __launch_bounds__(256) void zerofill_kernel(const float* y, float* x,
 // (+ aux in modes 1-3); the summation order over the taps is the one of round 1 (k ascending), results unchanged.
 constexpr int BL_MAXW = 2048 + 128;       // longest staged line (image side <= 2048, ntaps <= 127)
 
+// ZERO: samples outside the image are 0 (the zero-boundary blur, DEG_BLUR_ZERO) instead of wrapped; resolved while staging, like the wrap
+template <bool ZERO>
 __global__ __launch_bounds__(256) void blur_rows_kernel(const float* __restrict__ in, float* __restrict__ out, const float* __restrict__ taps,
                                                        int ntaps, int rows, int W, int sign, int mode,
                                                        const float* __restrict__ aux, const float* __restrict__ coef, int rows_per_image) {
@@ -140,8 +142,13 @@ __global__ __launch_bounds__(256) void blur_rows_kernel(const float* __restrict_
     const size_t row0 = (size_t)blockIdx.x * blockDim.y;
     for (int i = tid; i < rows_here * LW; i += nthr) {
         const int rr = i / LW, j = i % LW;
-        int xx = (j - r) % W; xx += xx < 0 ? W : 0;
-        s_line[rr * LW + j] = in[(row0 + rr) * W + xx];
+        if (ZERO) {
+            const int xx = j - r;
+            s_line[rr * LW + j] = (xx >= 0 && xx < W) ? in[(row0 + rr) * W + xx] : 0.f;
+        } else {
+            int xx = (j - r) % W; xx += xx < 0 ? W : 0;
+            s_line[rr * LW + j] = in[(row0 + rr) * W + xx];
+        }
     }
     __syncthreads();
     if ((int)threadIdx.y >= rows_here) return;
@@ -183,6 +190,7 @@ __global__ __launch_bounds__(256) void blur_rows_kernel(const float* __restrict_
 }
 
 constexpr int BL_COLS = 32;
+template <bool ZERO>
 __global__ __launch_bounds__(256) void blur_cols_kernel(const float* __restrict__ in, float* __restrict__ out, const float* __restrict__ taps,
                                                        int ntaps, int H, int W, int sign, int mode,
                                                        const float* __restrict__ aux, const float* __restrict__ coef, int planes_per_image) {
@@ -195,8 +203,13 @@ __global__ __launch_bounds__(256) void blur_cols_kernel(const float* __restrict_
     const float* src = in + (size_t)plane * H * W;
     for (int i = tid; i < LH * BL_COLS; i += 256) {
         const int j = i / BL_COLS, cx = i % BL_COLS;
-        int yy = (j - r) % H; yy += yy < 0 ? H : 0;
-        s_col[i] = (x0 + cx < W) ? src[(size_t)yy * W + x0 + cx] : 0.f;
+        if (ZERO) {
+            const int yy = j - r;
+            s_col[i] = (x0 + cx < W && yy >= 0 && yy < H) ? src[(size_t)yy * W + x0 + cx] : 0.f;
+        } else {
+            int yy = (j - r) % H; yy += yy < 0 ? H : 0;
+            s_col[i] = (x0 + cx < W) ? src[(size_t)yy * W + x0 + cx] : 0.f;
+        }
     }
     __syncthreads();
     const int b = plane / planes_per_image;
@@ -250,7 +263,7 @@ static inline dim3 grid_for(int n_per_image, int B) {
 // re-reads (2.1x at r = 7, TS = 32) are L2 hits.  Odd tap counts with 2r < min(H, W) and r <= 24 only (the Gaussian's visible taps: 15
 // at sigma 1, 43 at sigma 3); anything else keeps the two-pass path.  mode / sign as above; the taps are flipped once for the
 // convolution so that both directions are the correlation  out[i] = sum_k g'[k] in[i - r + k].
-template <int TS>
+template <int TS, bool ZERO = false>
 __global__ __launch_bounds__(256) void blur2d_fused_kernel(const float* __restrict__ in, float* __restrict__ out, const float* __restrict__ taps,
                                                           int ntaps, int H, int W, int sign, int mode,
                                                           const float* __restrict__ aux, const float* __restrict__ coef, int planes_per_image) {
@@ -266,6 +279,10 @@ __global__ __launch_bounds__(256) void blur2d_fused_kernel(const float* __restri
     for (int i = tid; i < PW * PW; i += 256) {
         const int py = i / PW, px = i - py * PW;
         int gy = y0 - r + py, gx = x0 - r + px;
+        if (ZERO) {
+            s_in[py * PWP + px] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? src[(size_t)gy * W + gx] : 0.f;
+            continue;
+        }
         gy += gy < 0 ? H : 0; gy -= gy >= H ? H : 0; gy -= gy >= H ? H : 0;      // (a tile past the image edge wraps twice at most: TS + r < 2H)
         gx += gx < 0 ? W : 0; gx -= gx >= W ? W : 0; gx -= gx >= W ? W : 0;
         s_in[py * PWP + px] = src[(size_t)gy * W + gx];
@@ -311,43 +328,57 @@ __global__ __launch_bounds__(256) void blur2d_fused_kernel(const float* __restri
     }
 }
 
-static hipError_t blur2(const DegView& d, const float* in, float* tmp, float* out, int B, int C, int H, int W, int sign,
-                        int mode, const float* aux, const float* coef, hipStream_t s) {
-    if (W + d.ntaps > BL_MAXW || H + d.ntaps > BL_MAXW) return hipErrorInvalidValue;
-    static const bool fused_env = !(getenv("PNPFLOW_HIP_BLUR_FUSED") && atoi(getenv("PNPFLOW_HIP_BLUR_FUSED")) == 0);
-    if (fused_env && (d.ntaps & 1) && d.ntaps / 2 <= 24 && d.ntaps < H && d.ntaps < W && in != out &&
-        (d.ntaps / 2 <= 8 ? 32 : 64) + d.ntaps / 2 <= 2 * std::min(H, W)) {      // (the staging loop resolves at most two wraps)
-        const int r = d.ntaps / 2;
-        if (r <= 8) {
-            constexpr int TS = 32;
-            const int PW = TS + 2 * r;
-            const size_t lds = ((size_t)PW * (PW + 1) + 4 + (size_t)(PW + 3) * (TS + 1) + 128) * sizeof(float);
-            hipLaunchKernelGGL(blur2d_fused_kernel<TS>, dim3((W + TS - 1) / TS, (H + TS - 1) / TS, B * C), dim3(256), lds, s, in, out, d.taps, d.ntaps, H, W, sign, mode,
-                               aux, coef, C);
-        } else {
-            constexpr int TS = 64;
-            const int PW = TS + 2 * r;
-            const size_t lds = ((size_t)PW * (PW + 1) + 4 + (size_t)(PW + 3) * (TS + 1) + 128) * sizeof(float);
-            static unsigned long long attr64 = 0ull;
-            { hipError_t e = set_max_dynamic_lds_once(reinterpret_cast<const void*>(blur2d_fused_kernel<TS>), attr64, 160 * 1024); if (e != hipSuccess) return e; }
-            hipLaunchKernelGGL(blur2d_fused_kernel<TS>, dim3((W + TS - 1) / TS, (H + TS - 1) / TS, B * C), dim3(256), lds, s, in, out, d.taps, d.ntaps, H, W, sign, mode,
-                               aux, coef, C);
-        }
-        return hipGetLastError();
+template <int TS, bool ZERO>
+static hipError_t blur2_fused(const DegView& d, const float* in, float* out, int B, int C, int H, int W, int sign, int mode, const float* aux, const float* coef,
+                              hipStream_t s) {
+    const int r = d.ntaps / 2, PW = TS + 2 * r;
+    const size_t lds = ((size_t)PW * (PW + 1) + 4 + (size_t)(PW + 3) * (TS + 1) + 128) * sizeof(float);
+    if (TS == 64) {
+        static unsigned long long attr64 = 0ull;       // (one mask per instantiation: the attribute belongs to the kernel)
+        hipError_t e = set_max_dynamic_lds_once(reinterpret_cast<const void*>(blur2d_fused_kernel<TS, ZERO>), attr64, 160 * 1024);
+        if (e != hipSuccess) return e;
     }
+    hipLaunchKernelGGL((blur2d_fused_kernel<TS, ZERO>), dim3((W + TS - 1) / TS, (H + TS - 1) / TS, B * C), dim3(256), lds, s, in, out, d.taps, d.ntaps, H, W, sign, mode,
+                       aux, coef, C);
+    return hipGetLastError();
+}
+
+template <bool ZERO>
+static hipError_t blur2_passes(const DegView& d, const float* in, float* tmp, float* out, int B, int C, int H, int W, int sign, int mode, const float* aux,
+                               const float* coef, hipStream_t s) {
     const int r = d.ntaps / 2;
     // rows: 64-wide row groups, 256 threads per workgroup
     const int tx = 64, ty = 4, rows = B * C * H;
     const size_t lds_r = ((size_t)ty * (W + 2 * r + 4) + 128) * sizeof(float);
-    hipLaunchKernelGGL(blur_rows_kernel, dim3((rows + ty - 1) / ty), dim3(tx, ty), lds_r, s, in, tmp, d.taps, d.ntaps, rows, W, sign, 0,
+    hipLaunchKernelGGL(blur_rows_kernel<ZERO>, dim3((rows + ty - 1) / ty), dim3(tx, ty), lds_r, s, in, tmp, d.taps, d.ntaps, rows, W, sign, 0,
                        (const float*)nullptr, (const float*)nullptr, C * H);
     const size_t lds_c = ((size_t)(H + 2 * r + 4) * BL_COLS + 128) * sizeof(float);
     static unsigned long long attr_set = 0ull;
-    { hipError_t e = set_max_dynamic_lds_once(reinterpret_cast<const void*>(blur_cols_kernel), attr_set, 160 * 1024); if (e != hipSuccess) return e; }
+    { hipError_t e = set_max_dynamic_lds_once(reinterpret_cast<const void*>(blur_cols_kernel<ZERO>), attr_set, 160 * 1024); if (e != hipSuccess) return e; }
     if (lds_c > 160 * 1024) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(blur_cols_kernel, dim3((W + BL_COLS - 1) / BL_COLS, B * C), dim3(256), lds_c, s, (const float*)tmp, out, d.taps, d.ntaps,
+    hipLaunchKernelGGL(blur_cols_kernel<ZERO>, dim3((W + BL_COLS - 1) / BL_COLS, B * C), dim3(256), lds_c, s, (const float*)tmp, out, d.taps, d.ntaps,
                        H, W, sign, mode, aux, coef, C);
     return hipGetLastError();
+}
+
+// The zero-boundary kind (DEG_BLUR_ZERO) is the CORRELATION with the taps (F.conv2d, padding 'same'), its adjoint the convolution: the
+// callers' sign (+1 = H) is turned round for it.  It has no size restriction: a filter radius beyond the image only stages zeros.
+static hipError_t blur2(const DegView& d, const float* in, float* tmp, float* out, int B, int C, int H, int W, int sign,
+                        int mode, const float* aux, const float* coef, hipStream_t s) {
+    if (W + d.ntaps > BL_MAXW || H + d.ntaps > BL_MAXW) return hipErrorInvalidValue;
+    const bool zero = d.kind == DEG_BLUR_ZERO;
+    if (zero) sign = -sign;
+    static const bool fused_env = !(getenv("PNPFLOW_HIP_BLUR_FUSED") && atoi(getenv("PNPFLOW_HIP_BLUR_FUSED")) == 0);
+    const bool fused_shape = zero || (d.ntaps < H && d.ntaps < W &&
+                                      (d.ntaps / 2 <= 8 ? 32 : 64) + d.ntaps / 2 <= 2 * std::min(H, W));      // (the circular staging loop resolves at most two wraps)
+    if (fused_env && (d.ntaps & 1) && d.ntaps / 2 <= 24 && in != out && fused_shape) {
+        if (d.ntaps / 2 <= 8) return zero ? blur2_fused<32, true>(d, in, out, B, C, H, W, sign, mode, aux, coef, s)
+                                          : blur2_fused<32, false>(d, in, out, B, C, H, W, sign, mode, aux, coef, s);
+        return zero ? blur2_fused<64, true>(d, in, out, B, C, H, W, sign, mode, aux, coef, s)
+                    : blur2_fused<64, false>(d, in, out, B, C, H, W, sign, mode, aux, coef, s);
+    }
+    return zero ? blur2_passes<true>(d, in, tmp, out, B, C, H, W, sign, mode, aux, coef, s)
+                : blur2_passes<false>(d, in, tmp, out, B, C, H, W, sign, mode, aux, coef, s);
 }
 
 hipError_t launch_deg_H(const DegView& d, const float* x, float* y, int B, int C, int H, int W, float* scratch, hipStream_t s) {
@@ -362,8 +393,8 @@ hipError_t launch_deg_H(const DegView& d, const float* x, float* y, int B, int C
             hipLaunchKernelGGL(decimate_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65535)), dim3(256), 0, s, x, y, B * C, H, W, d.sf);
             return hipGetLastError();
         }
-        case DEG_BLUR:
-            if (!scratch || d.ntaps < 1 || d.ntaps > 127) return hipErrorInvalidValue;
+        case DEG_BLUR: case DEG_BLUR_ZERO:
+            if (!scratch || !d.taps || d.ntaps < 1 || d.ntaps > 127) return hipErrorInvalidValue;
             return blur2(d, x, scratch, y, B, C, H, W, +1, 0, nullptr, nullptr, s);
         case DEG_SR_FILTER: {      // y = decimate(filter (*) x)
             if (!scratch || d.ntaps < 1 || d.ntaps > 127 || d.sf <= 0 || H % d.sf || W % d.sf) return hipErrorInvalidValue;
@@ -390,8 +421,8 @@ hipError_t launch_deg_Hadj(const DegView& d, const float* y, float* x, int B, in
             hipLaunchKernelGGL(zerofill_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65535)), dim3(256), 0, s, y, x, B * C, H, W, d.sf);
             return hipGetLastError();
         }
-        case DEG_BLUR:
-            if (!scratch || d.ntaps < 1 || d.ntaps > 127) return hipErrorInvalidValue;
+        case DEG_BLUR: case DEG_BLUR_ZERO:
+            if (!scratch || !d.taps || d.ntaps < 1 || d.ntaps > 127) return hipErrorInvalidValue;
             return blur2(d, y, scratch, x, B, C, H, W, -1, 0, nullptr, nullptr, s);
         case DEG_SR_FILTER: {      // x = filter^T (*) zerofill(y)
             if (!scratch || d.ntaps < 1 || d.ntaps > 127 || d.sf <= 0 || H % d.sf || W % d.sf) return hipErrorInvalidValue;
@@ -473,8 +504,8 @@ hipError_t launch_grad_step(const DegView& d, const float* x, const float* y, co
                                    d.sf, laplace);
             else hipLaunchKernelGGL(grad_step_sr_kernel, g, dim3(256), 0, s, x, y, coef, z, C, H, W, d.sf, laplace);
             return hipGetLastError();
-        case DEG_BLUR: {
-            if (!scratch || d.ntaps < 1 || d.ntaps > 127) return hipErrorInvalidValue;
+        case DEG_BLUR: case DEG_BLUR_ZERO: {
+            if (!scratch || !d.taps || d.ntaps < 1 || d.ntaps > 127) return hipErrorInvalidValue;
             float* s0 = scratch;
             float* s1 = scratch + (size_t)B * C * H * W;
             hipError_t e = blur2(d, x, s0, s1, B, C, H, W, +1, laplace ? 3 : 1, y, nullptr, s);     // s1 = Hx - y  (or its sign)
@@ -730,6 +761,7 @@ __global__ __launch_bounds__(256) void ot_ode_vec_kernel(DegView d, const float*
 hipError_t launch_ot_ode_vec(const DegView& d, const float* x, const float* vt, const float* y, const float* one_minus_t, const float* rt2,
                              float sigma2, float* vec, int B, int C, int H, int W, hipStream_t s) {
     if (d.kind == DEG_BLUR) return hipErrorInvalidValue;   // Fourier-domain solve: launch_ot_ode_vec_blur (fft2.hip)
+    if (d.kind == DEG_BLUR_ZERO) return hipErrorInvalidValue;   // no closed form: launch_krylov_solve (krylov.hip)
     if (d.kind == DEG_SR && (d.sf <= 0 || H % d.sf || W % d.sf)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(ot_ode_vec_kernel, grid_for(C * H * W, B), dim3(256), 0, s, d, x, vt, y, one_minus_t, rt2, sigma2, vec, C, H, W);
     return hipGetLastError();
@@ -750,6 +782,25 @@ hipError_t launch_ot_ode_update(float* x, const float* vt, const float* vec, con
     const int64_t total = (int64_t)B * n;
     hipLaunchKernelGGL(ot_ode_update_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 4096)), dim3(256), 0, s, x, vt, vec, g,
                        one_minus_t, coef, delta, n, total);
+    return hipGetLastError();
+}
+
+// the generic branch (ot_ode.py:74-77, no closed-form solve): out = x + (1-t[b]) * v (residual 0: x1_hat, the product rounded before the
+// sum) or out = y - hx (residual 1: the right-hand side d of the Krylov solve, krylov.hip)
+__global__ __launch_bounds__(256) void ot_ode_generic_kernel(const float* a, const float* c, const float* omt, float* out, int residual, int n, int64_t total) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256)
+        out[i] = residual ? __fsub_rn(a[i], c[i]) : __fadd_rn(a[i], __fmul_rn(omt[i / n], c[i]));
+}
+
+hipError_t launch_ot_ode_x1hat(const float* x, const float* vt, const float* one_minus_t, float* x1, int B, int n, hipStream_t s) {
+    const int64_t total = (int64_t)B * n;
+    hipLaunchKernelGGL(ot_ode_generic_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 4096)), dim3(256), 0, s, x, vt, one_minus_t, x1, 0, n, total);
+    return hipGetLastError();
+}
+
+hipError_t launch_ot_ode_residual(const float* y, const float* hx, float* d, int B, int n, hipStream_t s) {
+    const int64_t total = (int64_t)B * n;
+    hipLaunchKernelGGL(ot_ode_generic_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 4096)), dim3(256), 0, s, y, hx, (const float*)nullptr, d, 1, n, total);
     return hipGetLastError();
 }
 

@@ -45,7 +45,7 @@ class Degradation:
             out = torch.empty((B, Cc, Hf // sf, Wf // sf), dtype=torch.float32, device=x.device)
         if B == 0:
             return out          # an empty shard (global batch smaller than the number of ranks): nothing to launch
-        n_scr = {_lib.PF_DEG_GAUSSIAN_BLUR: 1, _lib.PF_DEG_SR_FILTERED: 2}.get(self.kind, 0)
+        n_scr = {_lib.PF_DEG_GAUSSIAN_BLUR: 1, _lib.PF_DEG_GAUSSIAN_BLUR_ZERO: 1, _lib.PF_DEG_SR_FILTERED: 2}.get(self.kind, 0)
         scratch = torch.empty((n_scr, B, Cc, Hf, Wf), dtype=torch.float32, device=x.device) if n_scr else None
         fn = lib.pf_degradation_H_adj if adjoint else lib.pf_degradation_H
         _lib.check(fn(C.byref(d), x.data_ptr(), out.data_ptr(), B, Cc, Hf, Wf,
@@ -187,15 +187,20 @@ class PaintbrushInpainting(Degradation):
 
 
 class GaussianDeblurring(Degradation):
-    """reference pnpflow/degradations.py:55-89, mode 'fft': circular convolution with the
+    """reference pnpflow/degradations.py:55-89.  mode 'fft': circular convolution with the
     61x61 normalised Gaussian (utils.py:273-280).  The kernel is exactly separable, so the
-    engine runs two 1-D circular passes instead of three FFTs per call."""
+    engine runs two 1-D circular passes instead of three FFTs per call.
+    Any other mode (the reference's own rule, degradations.py:72-76, 82-86): F.conv2d(padding='same') with the same kernel, i.e. the
+    blur whose samples outside the image are 0 (PF_DEG_GAUSSIAN_BLUR_ZERO); zero extension commutes with the two 1-D passes, and the
+    kernel is symmetric, so H_adj = H.  An even kernel_size is refused there: padding='same' is asymmetric for it."""
     kind = _lib.PF_DEG_GAUSSIAN_BLUR
 
     def __init__(self, sigma_blur, kernel_size, mode="fft", num_channels=3, dim_image=128, device="cuda"):
         super().__init__()
         if mode != "fft":
-            raise NotImplementedError("only the circular ('fft') mode used by main.py is implemented")
+            if kernel_size % 2 == 0:
+                raise ValueError(f"GaussianDeblurring(mode={mode!r}): kernel_size must be odd (padding='same' is asymmetric for an even kernel), got {kernel_size}")
+            self.kind = _lib.PF_DEG_GAUSSIAN_BLUR_ZERO
         self.mode, self.sigma, self.kernel_size = mode, sigma_blur, kernel_size
         ax = np.arange(-kernel_size // 2 + 1.0, kernel_size // 2 + 1.0)
         g = np.exp(-(ax ** 2) / (2 * sigma_blur ** 2))

@@ -93,6 +93,9 @@ class PROX_PNP(object):
             return 1
         if algo == "hqs" and problem == "gaussian_deblurring_FFT":
             return 2
+        if algo == "hqs" and problem == "gaussian_deblurring":
+            raise ValueError("pnp_gs: algo 'hqs' has no form for problem 'gaussian_deblurring' (the zero-boundary blur): its prox is a Fourier solve of the "
+                             "circular operator (problem 'gaussian_deblurring_FFT'); use algo 'pgd'")
         raise ValueError(f"pnp_gs: algo {algo!r} with problem {problem!r} is not supported; supported: {SUPPORTED}")
 
     def level_table(self, sigma_noise):
