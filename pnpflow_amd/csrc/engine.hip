@@ -111,16 +111,6 @@ struct Plan {
     float* nx_sigma = nullptr;         // NCSN++ retained forward: the divisor t * t_scale of its output, per image (read by the backward)
 };
 
-struct SolverBufs {
-    int B = 0; size_t n = 0, ny = 0; int steps = 0, ns = 0;
-    float *x = nullptr, *z = nullptr, *zt = nullptr, *v = nullptr, *scratch = nullptr, *y = nullptr;
-    unsigned long long* rng = nullptr;       // device [seed, stream_base, elem_offset]: read by the interpolation kernel, so that one
-                                             // captured graph serves every batch / shard
-    int64_t bytes = 0;
-    float *t_all = nullptr, *coef_all = nullptr, *t_cur = nullptr, *coef_cur = nullptr;
-    int* iter = nullptr;
-};
-
 }  // namespace
 
 struct NxMod {                 // one entry of NCSNpp.all_modules (ncsnpp.py:72-206), in construction order
@@ -129,7 +119,11 @@ struct NxMod {                 // one entry of NCSNpp.all_modules (ncsnpp.py:72-
     bool up = false, down = false;
 };
 
-struct DFlowState;                 // D-Flow / dopri5 buffers and graphs (engine_dflow.inc)
+struct CachedGraph;                // solver_rt.inc
+struct SolverBufs;                 // PnP-Flow buffers and graph (below, with pf_pnp_flow_restore)
+struct OdeBufs;                    // OT-ODE buffers and graphs (below, with pf_ot_ode_restore)
+struct DFlowState;                 // D-Flow buffers and graphs (engine_dflow.inc)
+struct DopriState;                 // dopri5 buffers (engine_dflow.inc)
 struct PnpGsState;                 // Prox-PnP (gradient-step denoiser) buffers and graph (engine_pnp_gs.inc)
 struct FlowPriorsState;            // Flow-Priors buffers (engine_flow_priors.inc)
 struct PriorEvalState;             // divergence / Euler sampler / likelihood solve buffers (engine_prior_eval.inc)
@@ -163,29 +157,19 @@ struct pf_engine {
     int retained_B = 0;
     uint64_t plan_clock = 0;         // LRU stamp source for the plan cache
     int64_t bytes = 0;               // device bytes currently held by this engine (weights, activation plans, solver buffers)
-    // cached hipGraph of one PnP-Flow outer iteration (re-used while the captured arguments stay the same)
-    struct GraphKey { const void* plan; int kind, half, sf, ntaps; const void* mask; const void* taps; const void* noise;
-                      int num_samples, batch_samples, noise_model, B; };
-    GraphKey gkey{}; hipGraph_t graph = nullptr; hipGraphExec_t gexec = nullptr;
     int precision = 1;   // 1 (default): split-fp16 (3 x f16 MFMA, fp32-equivalent) for the packed-weight convs; 0: exact fp32 MFMA;
                          // 2: single fp16 MFMA per product (fp16 operands, fp32 accumulate - TF32-class, include/pnpflow_hip.h)
-    SolverBufs sb;
-    // OT-ODE loop (pf_ot_ode_restore): iterate, velocity, solve output, J^T vec, per-iteration schedule tables, cached graph
-    struct OdeBufs { int B = 0; size_t n = 0, ny = 0; int steps = 0; int solve = 0 /* 0 closed form, 1 Fourier (circular blur), 2 Krylov (zero-boundary blur) */;
-                     float *x = nullptr, *vt = nullptr, *vec = nullptr, *g = nullptr, *y = nullptr, *scratch = nullptr;
-                     float *dres = nullptr, *sol = nullptr, *kry = nullptr /* Krylov right-hand side, solution, workspace */; size_t kry_floats = 0;
-                     float *tab = nullptr /* [4][steps]: t, 1-t, r_t^2, coef */, *cur = nullptr /* [4][B] */; int* iter = nullptr; int64_t bytes = 0; } ob;
-    struct OdeKey { const void* plan; int kind, half, sf, ntaps; const void* mask; const void* taps; int B; float sigma2, delta; int pad_; };   // compared with memcmp: no implicit padding (static_assert below)
-    OdeKey okey{}; hipGraph_t ograph = nullptr; hipGraphExec_t ogexec = nullptr;
-    hipGraph_t ograph2 = nullptr; hipGraphExec_t ogexec2 = nullptr;      // Krylov solve: the step is two captured halves (ograph: up to d, ograph2: from H_adj(sol)) with the Krylov loop between them
+    // solver state, one heap struct per family: each owns its device buffers (DevBufs) and cached graphs (solver_rt.inc)
+    SolverBufs* sb = nullptr;            // pf_pnp_flow_restore
+    OdeBufs* ob = nullptr;               // pf_ot_ode_restore
     int64_t ode_krylov_iters = 0;        // Krylov iterations enqueued by the last pf_ot_ode_restore
     hipStream_t work_stream = nullptr;   // used when the caller passes the NULL stream and asks for graph replay
-    DFlowState* dflow = nullptr;         // pf_d_flow_* / pf_flow_ode_dopri5 state (engine_dflow.inc)
-    const void* held_plans[3] = {};      // plans a cached D-Flow graph replays (kept out of the plan cache's eviction)
+    DFlowState* dflow = nullptr;         // pf_d_flow_forward / pf_d_flow_value_and_grad state (engine_dflow.inc)
+    DopriState* dopri = nullptr;         // pf_flow_ode_dopri5 state (engine_dflow.inc)
     PnpGsState* pnpgs = nullptr;         // pf_gs_denoiser_grad / pf_pnp_gs_restore state (engine_pnp_gs.inc)
-    const void* held_pnpgs_plan = nullptr;   // the plan its cached graph replays (kept out of the eviction as well)
     PriorEvalState* prior = nullptr;     // pf_flow_divergence / pf_flow_ode_euler / pf_flow_likelihood_rk45 state (engine_prior_eval.inc)
     FlowPriorsState* fprior = nullptr;   // pf_flow_priors_grad / pf_flow_priors_restore state (engine_flow_priors.inc)
+    std::vector<CachedGraph*> graphs;    // every live cached graph of the states above (CachedGraph::capture / drop keep the list)
     // profiling
     bool profile = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
@@ -227,6 +211,8 @@ struct DeviceGuard {
             return PF_ERR_HIP;                                                                 \
         }                                                                                      \
     } while (0)
+
+#include "solver_rt.inc"
 
 // --------------------------------------------------------------------------------------
 // architecture walk (models.py:337-436) -> descriptors + expected state_dict entries
@@ -913,13 +899,11 @@ static int build_plan(pf_engine* e, int B, bool retain, Plan** out_plan) {
     auto it = e->plans.find(key);
     if (it != e->plans.end()) { *out_plan = e->last_plan = it->second.get(); it->second->last_used = ++e->plan_clock; return PF_OK; }
     // bounded cache: a plan owns its activation buffers (GBs at the BASELINE sizes), so the least recently used one is
-    // dropped before a ninth is built (never the retained one a pf_unet_backward may still walk, nor the graph's)
+    // dropped before a ninth is built (never the retained one a pf_unet_backward may still walk, nor one a cached graph replays)
     while (e->plans.size() >= 8) {
         auto victim = e->plans.end();
         for (auto jt = e->plans.begin(); jt != e->plans.end(); ++jt) {
-            if (jt->second.get() == e->retained_plan || jt->second.get() == e->gkey.plan || jt->second.get() == e->okey.plan) continue;
-            if (jt->second.get() == e->held_plans[0] || jt->second.get() == e->held_plans[1] || jt->second.get() == e->held_plans[2]) continue;
-            if (jt->second.get() == e->held_pnpgs_plan) continue;
+            if (jt->second.get() == e->retained_plan || plan_is_held(e, jt->second.get())) continue;
             if (victim == e->plans.end() || jt->second->last_used < victim->second->last_used) victim = jt;
         }
         if (victim == e->plans.end()) break;
@@ -1514,17 +1498,9 @@ int pf_ncsnpp_create(int device_id, const pf_ncsnpp_cfg* cfg, pf_engine** out) {
     return PF_OK;
 }
 
-static void drop_graph(pf_engine* e);
-static void drop_ode_graph(pf_engine* e);
-static void drop_dflow_graphs(pf_engine* e);
-static void free_dflow(pf_engine* e);
-static void drop_pnpgs_graph(pf_engine* e);
-static void free_pnpgs(pf_engine* e);
-static void free_prior(pf_engine* e);
-static void free_fprior(pf_engine* e);
 int pf_engine_set_solver_time_scale(pf_engine* e, float scale) {
     if (!e || !(scale > 0.f)) return PF_ERR_INVALID;
-    if (scale != e->solver_time_scale) { drop_graph(e); drop_ode_graph(e); drop_dflow_graphs(e); drop_pnpgs_graph(e); e->solver_time_scale = scale; }   // the captured graphs bake the scale in
+    if (scale != e->solver_time_scale) { drop_all_graphs(e); e->solver_time_scale = scale; }   // the captured graphs bake the scale in
     return PF_OK;
 }
 
@@ -1553,37 +1529,15 @@ static int check_flags(pf_engine* e) {
     return PF_OK;
 }
 
-static void free_ode(pf_engine* e);
-
-static void drop_graph(pf_engine* e) {
-    if (e->gexec) hipGraphExecDestroy(e->gexec);
-    if (e->graph) hipGraphDestroy(e->graph);
-    e->gexec = nullptr; e->graph = nullptr; e->gkey = pf_engine::GraphKey{};
-}
-
-static void free_solver(pf_engine* e) {
-    drop_graph(e);          // its nodes point into the solver buffers
-    SolverBufs& b = e->sb;
-    for (void* p : {(void*)b.x, (void*)b.z, (void*)b.zt, (void*)b.v, (void*)b.scratch, (void*)b.y, (void*)b.rng, (void*)b.t_all,
-                    (void*)b.coef_all, (void*)b.t_cur, (void*)b.coef_cur, (void*)b.iter})
-        if (p) hipFree(p);
-    e->bytes -= b.bytes;
-    b = SolverBufs{};
-}
+static void free_solver_states(pf_engine* e);       // at the end of this file, where every state struct is complete
 
 void pf_engine_destroy(pf_engine* e) {
     if (!e) return;
     hipSetDevice(e->device);
-    drop_graph(e);
-    free_ode(e);
-    free_dflow(e);
-    free_pnpgs(e);
-    free_prior(e);
-    free_fprior(e);
+    free_solver_states(e);      // graphs and buffers first: the graphs' nodes point into the plans freed below
     for (auto& kv : e->plans) for (void* p : kv.second->allocs) hipFree(p);
     for (void* p : e->weight_allocs) hipFree(p);
     for (auto& ev : e->ev_pool) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
-    free_solver(e);
     if (e->work_stream) hipStreamDestroy(e->work_stream);
     delete e;
 }
@@ -1634,7 +1588,7 @@ int pf_engine_finalize_weights(pf_engine* e) {
 int pf_engine_set_precision(pf_engine* e, int mode) {
     if (!e) return PF_ERR_INVALID;
     if (mode < 0 || mode > 2) { e->err = "precision mode must be 0 (fp32 MFMA), 1 (split-fp16 MFMA, fp32-equivalent) or 2 (single fp16 MFMA)"; return PF_ERR_INVALID; }
-    if (mode != e->precision) { drop_graph(e); drop_ode_graph(e); drop_dflow_graphs(e); drop_pnpgs_graph(e); }       // captured graphs bake the kernel choice in
+    if (mode != e->precision) drop_all_graphs(e);       // captured graphs bake the kernel choice in
     e->precision = mode;
     return PF_OK;
 }
@@ -1809,28 +1763,41 @@ int pf_ssim(const float* rec, const float* clean, double* out, int B, int C, int
     return PF_OK;
 }
 
+struct SolverBufs {
+    int B = 0; size_t n = 0, ny = 0; int steps = 0, ns = 0;
+    float *x = nullptr, *z = nullptr, *zt = nullptr, *v = nullptr, *scratch = nullptr, *y = nullptr;
+    unsigned long long* rng = nullptr;       // device [seed, stream_base, elem_offset]: read by the interpolation kernel, so that one
+                                             // captured graph serves every batch / shard
+    float *t_all = nullptr, *coef_all = nullptr, *t_cur = nullptr, *coef_cur = nullptr;
+    int* iter = nullptr;
+    DevBufs mem;
+    // cached hipGraph of one outer iteration (re-used while the captured arguments stay the same)
+    struct Key { const void* plan; int kind, half, sf, ntaps; const void* mask; const void* taps; const void* noise;
+                 int num_samples, batch_samples, noise_model, B; };
+    static_assert(sizeof(Key) == 4 * sizeof(void*) + 8 * sizeof(int), "SolverBufs::Key is compared with memcmp: it must have no padding bytes");
+    CachedGraph graph;
+    void reset(pf_engine* e) { graph.drop(e); /* its nodes point into the buffers */ mem.release(e); *this = SolverBufs{}; }
+};
+
 static int ensure_solver(pf_engine* e, int B, size_t n, size_t ny, int steps, int ns) {
-    SolverBufs& b = e->sb;
+    if (!e->sb) e->sb = new SolverBufs();
+    SolverBufs& b = *e->sb;
     if (b.B == B && b.n == n && b.ny == ny && b.steps >= steps && b.ns >= ns) return PF_OK;
-    free_solver(e);
+    b.reset(e);
     const size_t tot = (size_t)B * n;
-    HIPCHK(e, hipMalloc(&b.x, tot * 4)); HIPCHK(e, hipMalloc(&b.z, tot * 4)); HIPCHK(e, hipMalloc(&b.zt, ns * tot * 4));
-    HIPCHK(e, hipMalloc(&b.v, ns * tot * 4)); HIPCHK(e, hipMalloc(&b.scratch, 2 * tot * 4));
-    HIPCHK(e, hipMalloc(&b.t_all, (size_t)steps * 4)); HIPCHK(e, hipMalloc(&b.coef_all, (size_t)steps * 4));
-    HIPCHK(e, hipMalloc(&b.t_cur, (size_t)ns * B * 4)); HIPCHK(e, hipMalloc(&b.coef_cur, (size_t)ns * B * 4));
-    HIPCHK(e, hipMalloc(&b.iter, 64));
-    HIPCHK(e, hipMalloc(&b.y, (size_t)B * ny * 4)); HIPCHK(e, hipMalloc(&b.rng, 64));
-    if (poison_enabled()) { poison(b.x, tot * 4, 2); poison(b.z, tot * 4, 2); poison(b.zt, ns * tot * 4, 2); poison(b.v, ns * tot * 4, 2); poison(b.scratch, 2 * tot * 4, 2); poison(b.y, (size_t)B * ny * 4, 2);
-                            poison(b.t_cur, (size_t)ns * B * 4, 2); poison(b.coef_cur, (size_t)ns * B * 4, 2); }
+    int rc = PF_OK;
+    auto get = [&](auto** p, size_t bytes) { if (rc == PF_OK) rc = b.mem.alloc(e, p, bytes, 2); };
+    get(&b.x, tot * 4); get(&b.z, tot * 4); get(&b.zt, ns * tot * 4); get(&b.v, ns * tot * 4); get(&b.scratch, 2 * tot * 4);
+    get(&b.t_all, (size_t)steps * 4); get(&b.coef_all, (size_t)steps * 4); get(&b.t_cur, (size_t)ns * B * 4); get(&b.coef_cur, (size_t)ns * B * 4);
+    get(&b.iter, 64); get(&b.y, (size_t)B * ny * 4); get(&b.rng, 64);
+    if (rc != PF_OK) { b.reset(e); return rc; }
     b.B = B; b.n = n; b.ny = ny; b.steps = steps; b.ns = ns;
-    b.bytes = (int64_t)((1 + 1 + 2 * (size_t)ns + 2) * tot * 4 + (size_t)B * ny * 4 + 2 * (size_t)steps * 4 + 2 * (size_t)ns * B * 4 + 128);
-    e->bytes += b.bytes;
     return PF_OK;
 }
 
 static int enqueue_iteration(pf_engine* e, Plan* plan, const DegView& dv, const pf_pnp_params* prm, const float* y, int B, int C,
                              int H, hipStream_t s) {
-    SolverBufs& b = e->sb;
+    SolverBufs& b = *e->sb;
     const int n = C * H * H;
     const int nsb = prm->batch_samples ? prm->num_samples : 1;
     hipLaunchKernelGGL(prep_iter_kernel, dim3(1), dim3(64), 0, s, (const int*)b.iter, (const float*)b.t_all, (const float*)b.coef_all,
@@ -1876,24 +1843,15 @@ int pf_pnp_flow_restore(pf_engine* e, const pf_degradation* d, const pf_pnp_para
     if (!e->finalized) { e->err = "weights not finalized"; return PF_ERR_STATE; }
     USE_DEVICE(e);
     hipStream_t s = (hipStream_t)stream;
-    if (prm->use_graph && s == nullptr) {
-        // the legacy NULL stream cannot be captured: run on an engine-owned stream, ordered after everything already
-        // enqueued on the NULL stream (the function synchronises before returning).  The stream is a BLOCKING one
-        // (hipStreamDefault): work a callback puts on the NULL stream and the engine's next launches stay ordered by the
-        // legacy-stream rule (round 2: on a non-blocking stream, metric kernels launched from the callbacks on the NULL
-        // stream and cached-graph replays produced NaNs on the second batch; the Python solvers also hand over a real stream)
-        if (!e->work_stream) HIPCHK(e, hipStreamCreateWithFlags(&e->work_stream, hipStreamDefault));
-        HIPCHK(e, hipStreamSynchronize(nullptr));
-        s = e->work_stream;
-    }
+    int rc = graph_stream(e, prm->use_graph, s);
+    if (rc != PF_OK) return rc;
     const int C = e->cfg.input_channels, H = e->cfg.input_height;
     if (e->cfg.output_channels != C) { e->err = "restoration needs output_channels == input_channels"; return PF_ERR_INVALID; }
     const size_t n = (size_t)C * H * H;
     const int Hy = (d->kind == PF_DEG_SUPERRESOLUTION || d->kind == PF_DEG_SR_FILTERED) ? H / std::max(1, d->sf) : H;
     const size_t ny = (size_t)C * Hy * Hy;
-    int rc = ensure_solver(e, B, n, ny, prm->steps, prm->batch_samples ? prm->num_samples : 1);
-    if (rc != PF_OK) return rc;
-    SolverBufs& b = e->sb;
+    if ((rc = ensure_solver(e, B, n, ny, prm->steps, prm->batch_samples ? prm->num_samples : 1)) != PF_OK) return rc;
+    SolverBufs& b = *e->sb;
     Plan* plan = nullptr;
     if ((rc = build_plan(e, prm->batch_samples ? B * prm->num_samples : B, false, &plan)) != PF_OK) return rc;
     const DegView dv = to_view(d);
@@ -1911,25 +1869,14 @@ int pf_pnp_flow_restore(pf_engine* e, const pf_degradation* d, const pf_pnp_para
     // One outer iteration = one hipGraph (gradient step, interpolation, U-Net pass, average): iteration 0 runs eagerly (all
     // lazy initialisation done), the graph is captured once and kept while the captured arguments stay the same (every
     // per-batch / per-shard quantity - t, lr_t/sigma^2, noise streams, y - is read from engine-owned device buffers).
-    const pf_engine::GraphKey key{plan, dv.kind, dv.half, dv.sf, dv.ntaps, dv.mask, dv.taps, prm->noise, prm->num_samples,
-                                  prm->batch_samples, prm->noise_model, B};
-    if (e->gexec && memcmp(&key, &e->gkey, sizeof key) != 0) drop_graph(e);
+    SolverBufs::Key key; memset(&key, 0, sizeof key);
+    key = {plan, dv.kind, dv.half, dv.sf, dv.ntaps, dv.mask, dv.taps, prm->noise, prm->num_samples, prm->batch_samples, prm->noise_model, B};
+    b.graph.keep_for(e, key);
     const bool can_graph = prm->use_graph && !e->profile;
     for (int it = 0; it < prm->steps; ++it) {
-        if (can_graph && (it >= 1 || e->gexec)) {
-            if (!e->gexec) {
-                HIPCHK(e, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-                rc = enqueue_iteration(e, plan, dv, prm, b.y, B, C, H, s);
-                hipGraph_t g = nullptr;
-                hipError_t ce = hipStreamEndCapture(s, &g);
-                if (rc != PF_OK) { if (g) hipGraphDestroy(g); return rc; }
-                if (ce != hipSuccess) { e->err = std::string("hipStreamEndCapture: ") + hipGetErrorString(ce); return PF_ERR_HIP; }
-                e->graph = g;
-                hipError_t ie = hipGraphInstantiate(&e->gexec, e->graph, nullptr, nullptr, 0);
-                if (ie != hipSuccess) { drop_graph(e); e->err = std::string("hipGraphInstantiate: ") + hipGetErrorString(ie); return PF_ERR_HIP; }
-                memset(&e->gkey, 0, sizeof e->gkey); e->gkey = key;
-            }
-            HIPCHK(e, hipGraphLaunch(e->gexec, s));
+        if (can_graph && (it >= 1 || b.graph.live())) {
+            if (!b.graph.live() && (rc = b.graph.capture(e, s, key, {plan}, [&] { return enqueue_iteration(e, plan, dv, prm, b.y, B, C, H, s); })) != PF_OK) return rc;
+            if ((rc = b.graph.launch(e, s)) != PF_OK) return rc;
         } else {
             if ((rc = enqueue_iteration(e, plan, dv, prm, b.y, B, C, H, s)) != PF_OK) return rc;
         }
@@ -1962,64 +1909,58 @@ __global__ void ode_prep_kernel(const int* iter, const float* tab, int steps, fl
     for (int i = threadIdx.x; i < 4 * B; i += blockDim.x) cur[i] = tab[(i / B) * steps + it];
 }
 
-static void drop_ode_graph(pf_engine* e) {
-    if (e->ogexec) hipGraphExecDestroy(e->ogexec);
-    if (e->ograph) hipGraphDestroy(e->ograph);
-    if (e->ogexec2) hipGraphExecDestroy(e->ogexec2);
-    if (e->ograph2) hipGraphDestroy(e->ograph2);
-    e->ogexec = nullptr; e->ograph = nullptr; e->ogexec2 = nullptr; e->ograph2 = nullptr; e->okey = pf_engine::OdeKey{};
-}
-
-static void free_ode(pf_engine* e) {
-    drop_ode_graph(e);
-    auto& b = e->ob;
-    for (void* p : {(void*)b.x, (void*)b.vt, (void*)b.vec, (void*)b.g, (void*)b.y, (void*)b.scratch, (void*)b.tab, (void*)b.cur, (void*)b.iter, (void*)b.dres, (void*)b.sol, (void*)b.kry})
-        if (p) hipFree(p);
-    e->bytes -= b.bytes;
-    b = pf_engine::OdeBufs{};
-}
-
 constexpr int ODE_KRYLOV_MAX_ITER = 100;       // utils.GMRES(C_ope, d, max_iter=100), ot_ode.py:126-127; tol = atol = 1e-6 are its defaults
 
+// iterate, velocity, solve output, J^T vec, per-iteration schedule tables, cached graph(s)
+struct OdeBufs {
+    int B = 0; size_t n = 0, ny = 0; int steps = 0; int solve = 0 /* 0 closed form, 1 Fourier (circular blur), 2 Krylov (zero-boundary blur) */;
+    float *x = nullptr, *vt = nullptr, *vec = nullptr, *g = nullptr, *y = nullptr, *scratch = nullptr;
+    float *dres = nullptr, *sol = nullptr, *kry = nullptr /* Krylov right-hand side, solution, workspace */; size_t kry_floats = 0;
+    float *tab = nullptr /* [4][steps]: t, 1-t, r_t^2, coef */, *cur = nullptr /* [4][B] */; int* iter = nullptr;
+    DevBufs mem;
+    struct Key { const void* plan; int kind, half, sf, ntaps; const void* mask; const void* taps; int B; float sigma2, delta; int pad_; };
+    static_assert(sizeof(Key) == 3 * sizeof(void*) + 8 * sizeof(int), "OdeBufs::Key is compared with memcmp: it must have no padding bytes");
+    // the step as one graph; with the Krylov solve two captured halves under one key (graph: up to d, graph2: from H_adj(sol)) with the Krylov
+    // loop between them - captured together, dropped together
+    CachedGraph graph, graph2;
+    void drop_graphs(pf_engine* e) { graph.drop(e); graph2.drop(e); }
+    void reset(pf_engine* e) { drop_graphs(e); mem.release(e); *this = OdeBufs{}; }
+};
+
 static int ensure_ode(pf_engine* e, int B, size_t n, size_t ny, int steps, int solve, int H) {
-    auto& b = e->ob;
+    if (!e->ob) e->ob = new OdeBufs();
+    OdeBufs& b = *e->ob;
     if (b.B == B && b.n == n && b.ny == ny && b.steps >= steps && b.solve == solve) return PF_OK;
-    free_ode(e);
+    b.reset(e);
     const size_t tot = (size_t)B * n;
-    HIPCHK(e, hipMalloc(&b.x, tot * 4)); HIPCHK(e, hipMalloc(&b.vt, tot * 4)); HIPCHK(e, hipMalloc(&b.vec, tot * 4)); HIPCHK(e, hipMalloc(&b.g, tot * 4));
-    HIPCHK(e, hipMalloc(&b.y, (size_t)B * ny * 4));
+    int rc = PF_OK;
+    auto get = [&](auto** p, size_t bytes) { if (rc == PF_OK) rc = b.mem.alloc(e, p, bytes, 4); };
+    get(&b.x, tot * 4); get(&b.vt, tot * 4); get(&b.vec, tot * 4); get(&b.g, tot * 4); get(&b.y, (size_t)B * ny * 4);
     const size_t scr = solve == 1 ? 4 * tot + 2 * (size_t)H : solve == 2 ? tot : 0;
-    if (scr) HIPCHK(e, hipMalloc(&b.scratch, scr * 4));
-    size_t kry_bytes = 0;
+    if (scr) get(&b.scratch, scr * 4);
     if (solve == 2) {
-        HIPCHK(e, hipMalloc(&b.dres, tot * 4)); HIPCHK(e, hipMalloc(&b.sol, tot * 4));
-        b.kry_floats = krylov_workspace_floats(B, n, ODE_KRYLOV_MAX_ITER);
-        const hipError_t ke = hipMalloc(&b.kry, b.kry_floats * 4);
+        get(&b.dres, tot * 4); get(&b.sol, tot * 4);
+        const size_t want = krylov_workspace_floats(B, n, ODE_KRYLOV_MAX_ITER) * 4;
+        const hipError_t ke = rc == PF_OK ? b.mem.try_alloc(e, &b.kry, want, 4) : hipSuccess;
         if (ke != hipSuccess) {
             (void)hipGetLastError();
-            b.kry = nullptr;
-            const size_t want = b.kry_floats * 4;
-            b.B = 0; b.bytes = 0;        // (nothing is accounted yet: free_ode releases what was allocated)
-            free_ode(e);
+            b.reset(e);
             e->err = "ot_ode: cannot allocate the Krylov workspace of " + std::to_string(want) + " bytes (" + std::to_string(ODE_KRYLOV_MAX_ITER + 3) +
                      " x batch x image floats): " + hipGetErrorString(ke);
             return PF_ERR_HIP;
         }
-        kry_bytes = 2 * tot * 4 + b.kry_floats * 4;
-        if (poison_enabled()) { poison(b.dres, tot * 4, 4); poison(b.sol, tot * 4, 4); poison(b.kry, b.kry_floats * 4, 4); }
     }
-    HIPCHK(e, hipMalloc(&b.tab, (size_t)4 * steps * 4)); HIPCHK(e, hipMalloc(&b.cur, (size_t)4 * B * 4)); HIPCHK(e, hipMalloc(&b.iter, 64));
-    if (poison_enabled()) { for (float* q : {b.x, b.vt, b.vec, b.g}) poison(q, tot * 4, 4); poison(b.y, (size_t)B * ny * 4, 4); poison(b.scratch, scr * 4, 4); poison(b.tab, (size_t)4 * steps * 4, 4); poison(b.cur, (size_t)4 * B * 4, 4); }
+    get(&b.tab, (size_t)4 * steps * 4); get(&b.cur, (size_t)4 * B * 4); get(&b.iter, 64);
+    if (rc != PF_OK) { b.reset(e); return rc; }
+    b.kry_floats = solve == 2 ? krylov_workspace_floats(B, n, ODE_KRYLOV_MAX_ITER) : 0;
     b.B = B; b.n = n; b.ny = ny; b.steps = steps; b.solve = solve;
-    b.bytes = (int64_t)(4 * tot * 4 + (size_t)B * ny * 4 + scr * 4 + kry_bytes + (size_t)4 * steps * 4 + (size_t)4 * B * 4 + 64);
-    e->bytes += b.bytes;
     return PF_OK;
 }
 
 // one Euler step (ot_ode.py:67-147): every per-iteration scalar is read on the device from the schedule tables through the
 // iteration counter, so one captured graph serves every iteration
 static int enqueue_ode_step(pf_engine* e, Plan* plan, const DegView& dv, const pf_ot_ode_params* prm, int B, int C, int H, hipStream_t s) {
-    auto& b = e->ob;
+    OdeBufs& b = *e->ob;
     const int n = C * H * H;
     hipLaunchKernelGGL(ode_prep_kernel, dim3(1), dim3(256), 0, s, (const int*)b.iter, (const float*)b.tab, b.steps, b.cur, B);
     const float* t_cur = b.cur; const float* omt = b.cur + B; const float* rt2 = b.cur + 2 * B; const float* coef = b.cur + 3 * B;
@@ -2042,7 +1983,7 @@ static int enqueue_ode_step(pf_engine* e, Plan* plan, const DegView& dv, const p
 // half A  v_t = v_theta(x, t), d = y - H(x + (1-t) v_t);   [launch_krylov_solve: sol = (r_t^2 H H^T + sigma^2)^-1 d];   half B  vec = H_adj(sol),
 // g = J^T vec, update.  Each half is capturable on its own; the loop between them polls its done flags and therefore is not.
 static int enqueue_ode_krylov_a(pf_engine* e, Plan* plan, const DegView& dv, int B, int C, int H, hipStream_t s) {
-    auto& b = e->ob;
+    OdeBufs& b = *e->ob;
     const int n = C * H * H;
     hipLaunchKernelGGL(ode_prep_kernel, dim3(1), dim3(256), 0, s, (const int*)b.iter, (const float*)b.tab, b.steps, b.cur, B);
     const float* t_cur = b.cur; const float* omt = b.cur + B;
@@ -2056,7 +1997,7 @@ static int enqueue_ode_krylov_a(pf_engine* e, Plan* plan, const DegView& dv, int
 }
 
 static int enqueue_ode_krylov_b(pf_engine* e, Plan* plan, const DegView& dv, const pf_ot_ode_params* prm, int B, int C, int H, hipStream_t s) {
-    auto& b = e->ob;
+    OdeBufs& b = *e->ob;
     const int n = C * H * H;
     const float* omt = b.cur + B; const float* coef = b.cur + 3 * B;
     hipError_t r = launch_deg_Hadj(dv, b.sol, b.vec, B, C, H, H, b.scratch, s);
@@ -2068,20 +2009,6 @@ static int enqueue_ode_krylov_b(pf_engine* e, Plan* plan, const DegView& dv, con
     hipLaunchKernelGGL(bump_iter_kernel, dim3(1), dim3(64), 0, s, b.iter);
     r = hipGetLastError();
     if (r != hipSuccess) { e->err = std::string("ot_ode step: ") + hipGetErrorString(r); return PF_ERR_HIP; }
-    return PF_OK;
-}
-
-// captures fn() on s into *graph / *exec
-static int capture_ode_half(pf_engine* e, hipStream_t s, hipGraph_t* graph, hipGraphExec_t* exec, const std::function<int()>& fn) {
-    HIPCHK(e, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    const int rc = fn();
-    hipGraph_t g = nullptr;
-    const hipError_t ce = hipStreamEndCapture(s, &g);
-    if (rc != PF_OK) { if (g) hipGraphDestroy(g); return rc; }
-    if (ce != hipSuccess) { e->err = std::string("hipStreamEndCapture: ") + hipGetErrorString(ce); return PF_ERR_HIP; }
-    *graph = g;
-    const hipError_t ie = hipGraphInstantiate(exec, g, nullptr, nullptr, 0);
-    if (ie != hipSuccess) { drop_ode_graph(e); e->err = std::string("hipGraphInstantiate: ") + hipGetErrorString(ie); return PF_ERR_HIP; }
     return PF_OK;
 }
 
@@ -2111,11 +2038,8 @@ int pf_ot_ode_restore(pf_engine* e, const pf_degradation* d, const pf_ot_ode_par
     if (!e->finalized) { e->err = "weights not finalized"; return PF_ERR_STATE; }
     USE_DEVICE(e);
     hipStream_t s = (hipStream_t)stream;
-    if (prm->use_graph && s == nullptr) {
-        if (!e->work_stream) HIPCHK(e, hipStreamCreateWithFlags(&e->work_stream, hipStreamDefault));
-        HIPCHK(e, hipStreamSynchronize(nullptr));
-        s = e->work_stream;
-    }
+    int rc = graph_stream(e, prm->use_graph, s);
+    if (rc != PF_OK) return rc;
     const int C = e->cfg.input_channels, H = e->cfg.input_height;
     if (e->cfg.output_channels != C) { e->err = "restoration needs output_channels == input_channels"; return PF_ERR_INVALID; }
     if (d->kind == PF_DEG_SR_FILTERED) { e->err = "ot_ode: no closed-form solve for the filtered superresolution operator"; return PF_ERR_INVALID; }
@@ -2126,9 +2050,8 @@ int pf_ot_ode_restore(pf_engine* e, const pf_degradation* d, const pf_ot_ode_par
     const bool krylov = d->kind == PF_DEG_GAUSSIAN_BLUR_ZERO;
     if (krylov && (!d->taps || d->ntaps < 1 || d->ntaps > 127)) { e->err = "ot_ode: the zero-boundary blur needs 1 .. 127 device taps"; return PF_ERR_INVALID; }
     e->ode_krylov_iters = 0;
-    int rc = ensure_ode(e, B, n, ny, prm->steps, krylov ? 2 : d->kind == PF_DEG_GAUSSIAN_BLUR ? 1 : 0, H);
-    if (rc != PF_OK) return rc;
-    auto& b = e->ob;
+    if ((rc = ensure_ode(e, B, n, ny, prm->steps, krylov ? 2 : d->kind == PF_DEG_GAUSSIAN_BLUR ? 1 : 0, H)) != PF_OK) return rc;
+    OdeBufs& b = *e->ob;
     Plan* plan = nullptr;
     if ((rc = build_plan(e, B, true, &plan)) != PF_OK) return rc;
     e->retained_B = B; e->retained_plan = plan;
@@ -2145,41 +2068,28 @@ int pf_ot_ode_restore(pf_engine* e, const pf_degradation* d, const pf_ot_ode_par
     HIPCHK(e, hipMemcpyAsync(b.x, x_inout, (size_t)B * n * 4, hipMemcpyDeviceToDevice, s));
     HIPCHK(e, hipStreamSynchronize(s));      // the host tables may go away after return
 
-    static_assert(sizeof(pf_engine::OdeKey) == 3 * sizeof(void*) + 8 * sizeof(int), "OdeKey is compared with memcmp: it must have no padding bytes");
-    const pf_engine::OdeKey key{plan, dv.kind, dv.half, dv.sf, dv.ntaps, dv.mask, dv.taps, B, prm->sigma2, prm->delta, 0};
-    if (e->ogexec && memcmp(&key, &e->okey, sizeof key) != 0) drop_ode_graph(e);
+    OdeBufs::Key key; memset(&key, 0, sizeof key);
+    key = {plan, dv.kind, dv.half, dv.sf, dv.ntaps, dv.mask, dv.taps, B, prm->sigma2, prm->delta, 0};
+    if (!b.graph.keep_for(e, key)) b.drop_graphs(e);
     const bool can_graph = prm->use_graph && !e->profile;
     for (int it = first; it < prm->steps; ++it) {
+        const bool replay = can_graph && (it > first || b.graph.live());
         if (krylov) {
-            const bool replay = can_graph && (it > first || e->ogexec);
-            if (replay && !e->ogexec) {
-                if ((rc = capture_ode_half(e, s, &e->ograph, &e->ogexec, [&] { return enqueue_ode_krylov_a(e, plan, dv, B, C, H, s); })) != PF_OK) { drop_ode_graph(e); return rc; }
-                if ((rc = capture_ode_half(e, s, &e->ograph2, &e->ogexec2, [&] { return enqueue_ode_krylov_b(e, plan, dv, prm, B, C, H, s); })) != PF_OK) { drop_ode_graph(e); return rc; }
-                memset(&e->okey, 0, sizeof e->okey); e->okey = key;
+            if (replay && !b.graph.live()) {
+                if ((rc = b.graph.capture(e, s, key, {plan}, [&] { return enqueue_ode_krylov_a(e, plan, dv, B, C, H, s); })) == PF_OK)
+                    rc = b.graph2.capture(e, s, key, {plan}, [&] { return enqueue_ode_krylov_b(e, plan, dv, prm, B, C, H, s); });
+                if (rc != PF_OK) { b.drop_graphs(e); return rc; }
             }
-            if (replay) HIPCHK(e, hipGraphLaunch(e->ogexec, s));
-            else if ((rc = enqueue_ode_krylov_a(e, plan, dv, B, C, H, s)) != PF_OK) return rc;
+            if ((rc = replay ? b.graph.launch(e, s) : enqueue_ode_krylov_a(e, plan, dv, B, C, H, s)) != PF_OK) return rc;
             int ran = 0;
             const hipError_t kr = launch_krylov_solve(dv, b.cur + 2 * B, prm->sigma2, b.dres, b.sol, B, C, H, H, ODE_KRYLOV_MAX_ITER, 1e-6f, 1e-6f, b.kry, b.kry_floats,
                                                      nullptr, s, &ran);
             if (kr != hipSuccess) { e->err = std::string("ot_ode Krylov solve: ") + hipGetErrorString(kr); return PF_ERR_HIP; }
             e->ode_krylov_iters += ran;
-            if (replay) HIPCHK(e, hipGraphLaunch(e->ogexec2, s));
-            else if ((rc = enqueue_ode_krylov_b(e, plan, dv, prm, B, C, H, s)) != PF_OK) return rc;
-        } else if (can_graph && (it > first || e->ogexec)) {
-            if (!e->ogexec) {
-                HIPCHK(e, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-                rc = enqueue_ode_step(e, plan, dv, prm, B, C, H, s);
-                hipGraph_t g = nullptr;
-                hipError_t ce = hipStreamEndCapture(s, &g);
-                if (rc != PF_OK) { if (g) hipGraphDestroy(g); return rc; }
-                if (ce != hipSuccess) { e->err = std::string("hipStreamEndCapture: ") + hipGetErrorString(ce); return PF_ERR_HIP; }
-                e->ograph = g;
-                hipError_t ie = hipGraphInstantiate(&e->ogexec, e->ograph, nullptr, nullptr, 0);
-                if (ie != hipSuccess) { drop_ode_graph(e); e->err = std::string("hipGraphInstantiate: ") + hipGetErrorString(ie); return PF_ERR_HIP; }
-                memset(&e->okey, 0, sizeof e->okey); e->okey = key;
-            }
-            HIPCHK(e, hipGraphLaunch(e->ogexec, s));
+            if ((rc = replay ? b.graph2.launch(e, s) : enqueue_ode_krylov_b(e, plan, dv, prm, B, C, H, s)) != PF_OK) return rc;
+        } else if (replay) {
+            if (!b.graph.live() && (rc = b.graph.capture(e, s, key, {plan}, [&] { return enqueue_ode_step(e, plan, dv, prm, B, C, H, s); })) != PF_OK) return rc;
+            if ((rc = b.graph.launch(e, s)) != PF_OK) return rc;
         } else {
             if ((rc = enqueue_ode_step(e, plan, dv, prm, B, C, H, s)) != PF_OK) return rc;
         }
@@ -2234,3 +2144,8 @@ int pf_engine_profile_read(pf_engine* e, int64_t* launches, double* ms_conv_gemm
 #include "engine_pnp_gs.inc"
 #include "engine_prior_eval.inc"
 #include "engine_flow_priors.inc"
+
+// teardown: every solver state goes the way a shape change sends it (graphs dropped, buffers released), then its struct
+static void free_solver_states(pf_engine* e) {
+    free_state(e, e->sb); free_state(e, e->ob); free_state(e, e->dflow); free_state(e, e->dopri); free_state(e, e->pnpgs); free_state(e, e->prior); free_state(e, e->fprior);
+}

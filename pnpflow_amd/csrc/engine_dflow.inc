@@ -18,102 +18,57 @@ struct DFlowState {
     float *tab = nullptr;     // [2M][B]: t_i, then t_i + delta/2
     float *loss = nullptr, *coef = nullptr;              // [B]
     double* part = nullptr;   // [2][B][64]
-    int64_t bytes = 0;
     std::vector<float> host_tab;
     // cached graphs: T(z) and one closure
     struct FwdKey { const void* plan; int B, M; float delta, half_delta; int pad_; };
     struct VgKey { const void* plan_fwd; const void* plan_ret; int kind, half, sf, ntaps; const void* mask; const void* taps; int B, M;
                    float delta, half_delta, lmbda; int pad_; };
-    FwdKey fkey{}; hipGraph_t fgraph = nullptr; hipGraphExec_t fexec = nullptr;
-    VgKey vkey{}; hipGraph_t vgraph = nullptr; hipGraphExec_t vexec = nullptr;
-    // dopri5 state of one (B, n)
-    int oB = 0; size_t on = 0;
-    float *oy = nullptr, *oy1 = nullptr, *ostage = nullptr, *ok[7] = {}, *ot = nullptr;
-    double* opart = nullptr;  // [64] partials + [1] sum
-    int64_t obytes = 0;
+    static_assert(sizeof(FwdKey) == sizeof(void*) + 6 * sizeof(int), "FwdKey is compared with memcmp: it must have no padding bytes");
+    static_assert(sizeof(VgKey) == 4 * sizeof(void*) + 10 * sizeof(int), "VgKey is compared with memcmp: it must have no padding bytes");
+    CachedGraph fgraph, vgraph;
+    DevBufs mem;
+    void reset(pf_engine* e) { fgraph.drop(e); vgraph.drop(e); /* their nodes point into the buffers */ mem.release(e); *this = DFlowState{}; }
 };
 
-static void drop_dflow_graphs(pf_engine* e) {
-    DFlowState* st = e->dflow;
-    if (!st) return;
-    if (st->fexec) hipGraphExecDestroy(st->fexec);
-    if (st->fgraph) hipGraphDestroy(st->fgraph);
-    if (st->vexec) hipGraphExecDestroy(st->vexec);
-    if (st->vgraph) hipGraphDestroy(st->vgraph);
-    st->fexec = nullptr; st->fgraph = nullptr; st->vexec = nullptr; st->vgraph = nullptr;
-    st->fkey = DFlowState::FwdKey{}; st->vkey = DFlowState::VgKey{};
-    e->held_plans[0] = e->held_plans[1] = e->held_plans[2] = nullptr;
-}
-
-static void free_dflow_bufs(pf_engine* e) {
-    DFlowState* st = e->dflow;
-    drop_dflow_graphs(e);       // their nodes point into the buffers
-    for (void* p : {(void*)st->zs, (void*)st->us, (void*)st->zT, (void*)st->v, (void*)st->g, (void*)st->h, (void*)st->jg, (void*)st->grad, (void*)st->y,
-                    (void*)st->hx, (void*)st->r2, (void*)st->scr, (void*)st->tab, (void*)st->loss, (void*)st->coef, (void*)st->part})
-        if (p) hipFree(p);
-    e->bytes -= st->bytes;
-    st->zs = st->us = st->zT = st->v = st->g = st->h = st->jg = st->grad = st->y = st->hx = st->r2 = st->scr = st->tab = st->loss = st->coef = nullptr;
-    st->part = nullptr; st->bytes = 0; st->B = 0; st->n = st->ny = 0; st->M = 0; st->host_tab.clear();
-}
-
-static void free_dopri_bufs(pf_engine* e) {
-    DFlowState* st = e->dflow;
-    for (void* p : {(void*)st->oy, (void*)st->oy1, (void*)st->ostage, (void*)st->ot, (void*)st->opart}) if (p) hipFree(p);
-    for (float*& k : st->ok) { if (k) hipFree(k); k = nullptr; }
-    e->bytes -= st->obytes;
-    st->oy = st->oy1 = st->ostage = st->ot = nullptr; st->opart = nullptr; st->obytes = 0; st->oB = 0; st->on = 0;
-}
-
-static void free_dflow(pf_engine* e) {
-    if (!e->dflow) return;
-    free_dflow_bufs(e);
-    free_dopri_bufs(e);
-    delete e->dflow;
-    e->dflow = nullptr;
-}
-
-static int dflow_alloc(pf_engine* e, float** p, size_t floats, int64_t& bytes) {
-    HIPCHK(e, hipMalloc(p, std::max<size_t>(floats, 64) * 4));
-    poison(*p, std::max<size_t>(floats, 64) * 4, 4);
-    bytes += (int64_t)std::max<size_t>(floats, 64) * 4;
-    return PF_OK;
-}
+// dopri5 state of one (B, n): a set of its own beside the closure's, allocated and released independently of it
+struct DopriState {
+    int B = 0; size_t n = 0;
+    float *y = nullptr, *y1 = nullptr, *stage = nullptr, *k[7] = {}, *t = nullptr;
+    double* part = nullptr;   // [64] partials + [1] sum
+    DevBufs mem;
+    void reset(pf_engine* e) { mem.release(e); *this = DopriState{}; }
+};
 
 static int ensure_dflow(pf_engine* e, int B, size_t n, size_t ny, int M) {
     if (!e->dflow) e->dflow = new DFlowState();
     DFlowState* st = e->dflow;
     if (st->B == B && st->n == n && st->ny == ny && st->M == M) return PF_OK;
-    free_dflow_bufs(e);
+    st->reset(e);
     const size_t tot = (size_t)B * n, toty = (size_t)B * ny;
-    int64_t by = 0; int rc;
-    float** full[] = {&st->zT, &st->v, &st->g, &st->h, &st->jg, &st->grad};
-    for (float** p : full) if ((rc = dflow_alloc(e, p, tot, by)) != PF_OK) return rc;
-    if ((rc = dflow_alloc(e, &st->zs, (size_t)M * tot, by)) != PF_OK || (rc = dflow_alloc(e, &st->us, (size_t)M * tot, by)) != PF_OK ||
-        (rc = dflow_alloc(e, &st->y, toty, by)) != PF_OK || (rc = dflow_alloc(e, &st->hx, toty, by)) != PF_OK ||
-        (rc = dflow_alloc(e, &st->r2, toty, by)) != PF_OK || (rc = dflow_alloc(e, &st->scr, 2 * tot, by)) != PF_OK ||
-        (rc = dflow_alloc(e, &st->tab, (size_t)2 * M * B, by)) != PF_OK || (rc = dflow_alloc(e, &st->loss, B, by)) != PF_OK ||
-        (rc = dflow_alloc(e, &st->coef, B, by)) != PF_OK || (rc = dflow_alloc(e, (float**)&st->part, (size_t)2 * 2 * B * 64, by)) != PF_OK) {
-        st->bytes = by; e->bytes += by; free_dflow_bufs(e); return rc;
-    }
-    st->bytes = by; e->bytes += by;
+    int rc = PF_OK;
+    auto get = [&](auto** p, size_t count) { if (rc == PF_OK) rc = st->mem.alloc4(e, p, count); };
+    for (float** p : {&st->zT, &st->v, &st->g, &st->h, &st->jg, &st->grad}) get(p, tot);
+    get(&st->zs, (size_t)M * tot); get(&st->us, (size_t)M * tot);
+    for (float** p : {&st->y, &st->hx, &st->r2}) get(p, toty);
+    get(&st->scr, 2 * tot); get(&st->tab, (size_t)2 * M * B); get(&st->loss, B); get(&st->coef, B); get(&st->part, (size_t)2 * 2 * B * 64);
+    if (rc != PF_OK) { st->reset(e); return rc; }
     st->B = B; st->n = n; st->ny = ny; st->M = M;
     return PF_OK;
 }
 
 static int ensure_dopri(pf_engine* e, int B, size_t n) {
-    if (!e->dflow) e->dflow = new DFlowState();
-    DFlowState* st = e->dflow;
-    if (st->oB == B && st->on == n) return PF_OK;
-    free_dopri_bufs(e);
+    if (!e->dopri) e->dopri = new DopriState();
+    DopriState* st = e->dopri;
+    if (st->B == B && st->n == n) return PF_OK;
+    st->reset(e);
     const size_t tot = (size_t)B * n;
-    int64_t by = 0; int rc = PF_OK;
-    for (float** p : {&st->oy, &st->oy1, &st->ostage}) if (rc == PF_OK) rc = dflow_alloc(e, p, tot, by);
-    for (float*& k : st->ok) if (rc == PF_OK) rc = dflow_alloc(e, &k, tot, by);
-    if (rc == PF_OK) rc = dflow_alloc(e, &st->ot, B, by);
-    if (rc == PF_OK) rc = dflow_alloc(e, (float**)&st->opart, 2 * 72, by);
-    st->obytes = by; e->bytes += by;
-    if (rc != PF_OK) { free_dopri_bufs(e); return rc; }
-    st->oB = B; st->on = n;
+    int rc = PF_OK;
+    auto get = [&](auto** p, size_t count) { if (rc == PF_OK) rc = st->mem.alloc4(e, p, count); };
+    for (float** p : {&st->y, &st->y1, &st->stage}) get(p, tot);
+    for (float*& k : st->k) get(&k, tot);
+    get(&st->t, B); get(&st->part, 2 * 72);
+    if (rc != PF_OK) { st->reset(e); return rc; }
+    st->B = B; st->n = n;
     return PF_OK;
 }
 
@@ -178,36 +133,12 @@ static int enqueue_dflow_value_and_grad(pf_engine* e, Plan* pf, Plan* pr, const 
     return PF_OK;
 }
 
-// capture `enqueue` into (graph, exec) on s, or replay the cached one
-template <class F>
-static int dflow_run_graph(pf_engine* e, hipGraph_t& graph, hipGraphExec_t& exec, bool fresh, hipStream_t s, F enqueue) {
-    if (fresh) {
-        HIPCHK(e, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        int rc = enqueue();
-        hipGraph_t g = nullptr;
-        hipError_t ce = hipStreamEndCapture(s, &g);
-        if (rc != PF_OK) { if (g) hipGraphDestroy(g); return rc; }
-        if (ce != hipSuccess) { e->err = std::string("hipStreamEndCapture: ") + hipGetErrorString(ce); return PF_ERR_HIP; }
-        graph = g;
-        hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        if (ie != hipSuccess) { hipGraphDestroy(graph); graph = nullptr; exec = nullptr; e->err = std::string("hipGraphInstantiate: ") + hipGetErrorString(ie); return PF_ERR_HIP; }
-    }
-    HIPCHK(e, hipGraphLaunch(exec, s));
-    return PF_OK;
-}
-
-static int dflow_begin(pf_engine* e, const pf_d_flow_params* prm, int B, bool need_graph_stream, hipStream_t& s) {
+static int dflow_begin(pf_engine* e, const pf_d_flow_params* prm, bool need_graph_stream, hipStream_t& s) {
     if (!e->finalized) { e->err = "weights not finalized"; return PF_ERR_STATE; }
     int rc = dflow_check_prm(e, prm);
     if (rc != PF_OK) return rc;
     if (e->cfg.output_channels != e->cfg.input_channels) { e->err = "d_flow needs output_channels == input_channels"; return PF_ERR_INVALID; }
-    if (need_graph_stream && s == nullptr) {
-        if (!e->work_stream) HIPCHK(e, hipStreamCreateWithFlags(&e->work_stream, hipStreamDefault));
-        HIPCHK(e, hipStreamSynchronize(nullptr));
-        s = e->work_stream;
-    }
-    (void)B;
-    return PF_OK;
+    return graph_stream(e, need_graph_stream, s);
 }
 
 extern "C" {
@@ -217,7 +148,7 @@ int pf_d_flow_forward(pf_engine* e, const pf_d_flow_params* prm, const float* z,
     USE_DEVICE(e);
     hipStream_t s = (hipStream_t)stream;
     const bool can_graph = prm->use_graph && !e->profile;
-    int rc = dflow_begin(e, prm, B, can_graph, s);
+    int rc = dflow_begin(e, prm, can_graph, s);
     if (rc != PF_OK) return rc;
     const int C = e->cfg.input_channels, H = e->cfg.input_height;
     const size_t n = (size_t)C * H * H;
@@ -231,15 +162,10 @@ int pf_d_flow_forward(pf_engine* e, const pf_d_flow_params* prm, const float* z,
     if ((rc = dflow_upload_tab(e, prm, B, s)) != PF_OK) return rc;
     HIPCHK(e, hipMemcpyAsync(st->zs, z, (size_t)B * n * 4, hipMemcpyDeviceToDevice, s));
     if (can_graph) {
-        static_assert(sizeof(DFlowState::FwdKey) == sizeof(void*) + 6 * sizeof(int), "FwdKey is compared with memcmp: it must have no padding bytes");
-        DFlowState::FwdKey key{}; memset(&key, 0, sizeof key);
+        DFlowState::FwdKey key; memset(&key, 0, sizeof key);
         key.plan = plan; key.B = B; key.M = M; key.delta = prm->delta; key.half_delta = prm->half_delta;
-        const bool fresh = !st->fexec || memcmp(&key, &st->fkey, sizeof key) != 0;
-        if (fresh && st->fexec) {
-            hipGraphExecDestroy(st->fexec); hipGraphDestroy(st->fgraph); st->fexec = nullptr; st->fgraph = nullptr; e->held_plans[0] = nullptr;
-        }
-        if ((rc = dflow_run_graph(e, st->fgraph, st->fexec, fresh, s, [&] { return enqueue_dflow_forward(e, plan, prm, s); })) != PF_OK) return rc;
-        if (fresh) { st->fkey = key; e->held_plans[0] = plan; }
+        if (!st->fgraph.keep_for(e, key) && (rc = st->fgraph.capture(e, s, key, {plan}, [&] { return enqueue_dflow_forward(e, plan, prm, s); })) != PF_OK) return rc;
+        if ((rc = st->fgraph.launch(e, s)) != PF_OK) return rc;
     } else {
         if ((rc = enqueue_dflow_forward(e, plan, prm, s)) != PF_OK) return rc;
     }
@@ -253,18 +179,12 @@ int pf_d_flow_value_and_grad(pf_engine* e, const pf_degradation* d, const pf_d_f
     USE_DEVICE(e);
     hipStream_t s = (hipStream_t)stream;
     const bool can_graph = prm->use_graph && !e->profile;
-    int rc = dflow_begin(e, prm, B, can_graph, s);
+    int rc = dflow_begin(e, prm, can_graph, s);
     if (rc != PF_OK) return rc;
     const int C = e->cfg.input_channels, H = e->cfg.input_height;
     const size_t n = (size_t)C * H * H;
-    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_GAUSSIAN_BLUR_ZERO) { e->err = "d_flow: unknown degradation kind"; return PF_ERR_INVALID; }
-    const bool sr = d->kind == PF_DEG_SUPERRESOLUTION || d->kind == PF_DEG_SR_FILTERED;
-    if (sr && (d->sf <= 0 || H % d->sf)) { e->err = "d_flow: superresolution factor must divide the image size"; return PF_ERR_INVALID; }
-    if ((d->kind == PF_DEG_GAUSSIAN_BLUR || d->kind == PF_DEG_GAUSSIAN_BLUR_ZERO || d->kind == PF_DEG_SR_FILTERED) && (!d->taps || d->ntaps < 1 || d->ntaps > 127)) {
-        e->err = "d_flow: the filtered operators need 1..127 device taps"; return PF_ERR_INVALID;
-    }
-    if (d->kind == PF_DEG_MASK_INPAINTING && !d->mask) { e->err = "d_flow: mask inpainting needs a device mask"; return PF_ERR_INVALID; }
-    const int Hy = sr ? H / d->sf : H;
+    int Hy = 0;
+    if ((rc = check_operator(e, "d_flow", d, H, Hy)) != PF_OK) return rc;
     const size_t ny = (size_t)C * Hy * Hy;
     if (n % 4 || ny % 4) { e->err = "d_flow: C*H*W (and the measurement's C*Hy*Wy) must be multiples of 4"; return PF_ERR_INVALID; }
     const int M = prm->steps_euler - 1;
@@ -280,18 +200,12 @@ int pf_d_flow_value_and_grad(pf_engine* e, const pf_degradation* d, const pf_d_f
     HIPCHK(e, hipMemcpyAsync(st->y, y, (size_t)B * ny * 4, hipMemcpyDeviceToDevice, s));
     const DegView dv = to_view(d);
     if (can_graph) {
-        static_assert(sizeof(DFlowState::VgKey) == 4 * sizeof(void*) + 10 * sizeof(int), "VgKey is compared with memcmp: it must have no padding bytes");
-        DFlowState::VgKey key{}; memset(&key, 0, sizeof key);
+        DFlowState::VgKey key; memset(&key, 0, sizeof key);
         key.plan_fwd = pf; key.plan_ret = pr; key.kind = dv.kind; key.half = dv.half; key.sf = dv.sf; key.ntaps = dv.ntaps; key.mask = dv.mask;
         key.taps = dv.taps; key.B = B; key.M = M; key.delta = prm->delta; key.half_delta = prm->half_delta; key.lmbda = lmbda;
-        const bool fresh = !st->vexec || memcmp(&key, &st->vkey, sizeof key) != 0;
-        if (fresh && st->vexec) {
-            hipGraphExecDestroy(st->vexec); hipGraphDestroy(st->vgraph); st->vexec = nullptr; st->vgraph = nullptr;
-            e->held_plans[1] = e->held_plans[2] = nullptr;
-        }
-        if ((rc = dflow_run_graph(e, st->vgraph, st->vexec, fresh, s, [&] { return enqueue_dflow_value_and_grad(e, pf, pr, dv, prm, lmbda, s); })) != PF_OK)
-            return rc;
-        if (fresh) { st->vkey = key; e->held_plans[1] = pf; e->held_plans[2] = pr; }
+        if (!st->vgraph.keep_for(e, key) &&
+            (rc = st->vgraph.capture(e, s, key, {pf, pr}, [&] { return enqueue_dflow_value_and_grad(e, pf, pr, dv, prm, lmbda, s); })) != PF_OK) return rc;
+        if ((rc = st->vgraph.launch(e, s)) != PF_OK) return rc;
     } else {
         if ((rc = enqueue_dflow_value_and_grad(e, pf, pr, dv, prm, lmbda, s)) != PF_OK) return rc;
     }
@@ -328,7 +242,7 @@ int pf_flow_ode_dopri5(pf_engine* e, const pf_dopri5_params* prm, const float* x
     if (n % 4) { e->err = "dopri5: C*H*W must be a multiple of 4"; return PF_ERR_INVALID; }
     int rc = ensure_dopri(e, B, n);
     if (rc != PF_OK) return rc;
-    DFlowState* st = e->dflow;
+    DopriState* st = e->dopri;
     Plan* plan = nullptr;
     if ((rc = build_plan(e, B, false, &plan)) != PF_OK) return rc;
     const int64_t tot = (int64_t)B * n;
@@ -339,13 +253,13 @@ int pf_flow_ode_dopri5(pf_engine* e, const pf_dopri5_params* prm, const float* x
     const float sg = rev ? -1.f : 1.f;
     const double s0 = rev ? -prm->t0 : prm->t0, send = rev ? -prm->t1 : prm->t1;
     int64_t accepted = 0, rejected = 0, nfev = 0;
-    float* y = st->oy; float* y1 = st->oy1;
-    float** k = st->ok;
-    double* part = st->opart; double* red = st->opart + 64;
+    float* y = st->y; float* y1 = st->y1;
+    float** k = st->k;
+    double* part = st->part; double* red = st->part + 64;
     auto eval = [&](const float* yi, float s_f32, float* out) -> int {
-        DF_LAUNCH("time", launch_fill(st->ot, B, rev ? -s_f32 : s_f32, s));
+        DF_LAUNCH("time", launch_fill(st->t, B, rev ? -s_f32 : s_f32, s));
         ++nfev;
-        return run_plan(e, plan, yi, st->ot, out, s, e->solver_time_scale);
+        return run_plan(e, plan, yi, st->t, out, s, e->solver_time_scale);
     };
     auto rms = [&](const float* a, const float* b, const float* ya, const float* yb, const RkTerms& err, double& out) -> int {
         DF_LAUNCH("norm", launch_rk_norm(a, b, ya, yb, err, atol, rtol, part, red, tot, s));
@@ -363,8 +277,8 @@ int pf_flow_ode_dopri5(pf_engine* e, const pf_dopri5_params* prm, const float* x
     if ((rc = rms(y, nullptr, y, nullptr, none, d0)) != PF_OK) return rc;
     if ((rc = rms(k[0], nullptr, y, nullptr, none, d1)) != PF_OK) return rc;
     const float h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6f : (float)(0.01f * (float)d0 / (float)d1);
-    { RkTerms t{}; t.n = 1; t.k[0] = k[0]; t.c[0] = sg * h0; DF_LAUNCH("initial step", launch_rk_combine(y, t, st->ostage, tot, s)); }
-    if ((rc = eval(st->ostage, (float)s0 + h0, k[1])) != PF_OK) return rc;
+    { RkTerms t{}; t.n = 1; t.k[0] = k[0]; t.c[0] = sg * h0; DF_LAUNCH("initial step", launch_rk_combine(y, t, st->stage, tot, s)); }
+    if ((rc = eval(st->stage, (float)s0 + h0, k[1])) != PF_OK) return rc;
     if ((rc = rms(k[1], k[0], y, nullptr, none, d2)) != PF_OK) return rc;
     d2 = (double)std::fabs((float)d2 / h0);
     float h1;
@@ -386,7 +300,7 @@ int pf_flow_ode_dopri5(pf_engine* e, const pf_dopri5_params* prm, const float* x
             const float ti = kDpAlpha[i] == 1.0 ? (float)t1 : tf + (float)kDpAlpha[i] * dtf;
             RkTerms c{}; c.n = i + 1;
             for (int j = 0; j <= i; ++j) { c.k[j] = k[j]; c.c[j] = sg * ((float)kDpBeta[i][j] * dtf); }
-            float* yi = i == 5 ? y1 : st->ostage;                   // dopri5's last stage input is the 5th-order solution (FSAL)
+            float* yi = i == 5 ? y1 : st->stage;                   // dopri5's last stage input is the 5th-order solution (FSAL)
             DF_LAUNCH("stage", launch_rk_combine(y, c, yi, tot, s));
             if ((rc = eval(yi, ti, k[i + 1])) != PF_OK) return rc;
         }
@@ -400,9 +314,9 @@ int pf_flow_ode_dopri5(pf_engine* e, const pf_dopri5_params* prm, const float* x
             if (send <= t1) {     // last step: 4th-order dense output at send
                 RkTerms m{}; m.n = 7;
                 for (int j = 0; j < 7; ++j) { m.k[j] = k[j]; m.c[j] = sg * (dtf * (float)kDpMid[j]); }
-                DF_LAUNCH("midpoint", launch_rk_combine(y, m, st->ostage, tot, s));
+                DF_LAUNCH("midpoint", launch_rk_combine(y, m, st->stage, tot, s));
                 const float x = (float)((send - t) / (t1 - t));
-                DF_LAUNCH("dense output", launch_rk_interp(y, y1, st->ostage, k[0], k[6], sg, dtf, x, x_out, tot, s));
+                DF_LAUNCH("dense output", launch_rk_interp(y, y1, st->stage, k[0], k[6], sg, dtf, x, x_out, tot, s));
             }
             t = t1;
             std::swap(y, y1);
@@ -414,7 +328,7 @@ int pf_flow_ode_dopri5(pf_engine* e, const pf_dopri5_params* prm, const float* x
         if (ratio == 0.0) dt = dt * 10.0;
         else dt = dt * std::min(10.0, std::max(0.9 / std::pow(ratio, 1.0 / 5.0), ratio < 1.0 ? 1.0 : 0.2));
     }
-    st->oy = y; st->oy1 = y1;
+    st->y = y; st->y1 = y1;
     if (stats) { stats[0] = accepted; stats[1] = rejected; stats[2] = nfev; }
     HIPCHK(e, hipStreamSynchronize(s));
     return check_flags(e);

@@ -20,39 +20,22 @@ struct FlowPriorsState {
     float *y = nullptr, *hx = nullptr, *hxi = nullptr, *sd = nullptr;              // [B ny]
     float *scr = nullptr;                                                          // [2 B n]: H / H_adj scratch
     float *t = nullptr;                                                            // [B]
-    int64_t bytes = 0;
+    DevBufs mem;
+    void reset(pf_engine* e) { mem.release(e); *this = FlowPriorsState{}; }
 };
-
-static void free_fprior_bufs(pf_engine* e) {
-    FlowPriorsState* st = e->fprior;
-    for (void* p : {(void*)st->x, (void*)st->xi, (void*)st->pred, (void*)st->w, (void*)st->jw, (void*)st->xp, (void*)st->xm, (void*)st->jp, (void*)st->jm,
-                    (void*)st->ep, (void*)st->m, (void*)st->v, (void*)st->y, (void*)st->hx, (void*)st->hxi, (void*)st->sd, (void*)st->scr, (void*)st->t})
-        if (p) hipFree(p);
-    e->bytes -= st->bytes;
-    *st = FlowPriorsState{};
-}
-
-static void free_fprior(pf_engine* e) {
-    if (!e->fprior) return;
-    free_fprior_bufs(e);
-    delete e->fprior;
-    e->fprior = nullptr;
-}
 
 static int ensure_fprior(pf_engine* e, int B, size_t n, size_t ny) {
     if (!e->fprior) e->fprior = new FlowPriorsState();
     FlowPriorsState* st = e->fprior;
     if (st->B == B && st->n == n && st->ny == ny) return PF_OK;
-    free_fprior_bufs(e);
+    st->reset(e);
     const size_t tot = (size_t)B * n, toty = (size_t)B * ny;
-    int64_t by = 0; int rc = PF_OK;
-    for (float** p : {&st->x, &st->xi, &st->pred, &st->w, &st->jw, &st->xp, &st->xm, &st->jp, &st->jm, &st->ep, &st->m, &st->v})
-        if (rc == PF_OK) rc = dflow_alloc(e, p, tot, by);
-    for (float** p : {&st->y, &st->hx, &st->hxi, &st->sd}) if (rc == PF_OK) rc = dflow_alloc(e, p, toty, by);
-    if (rc == PF_OK) rc = dflow_alloc(e, &st->scr, 2 * tot, by);
-    if (rc == PF_OK) rc = dflow_alloc(e, &st->t, (size_t)B, by);
-    st->bytes = by; e->bytes += by;
-    if (rc != PF_OK) { free_fprior_bufs(e); return rc; }
+    int rc = PF_OK;
+    auto get = [&](auto** p, size_t count) { if (rc == PF_OK) rc = st->mem.alloc4(e, p, count); };
+    for (float** p : {&st->x, &st->xi, &st->pred, &st->w, &st->jw, &st->xp, &st->xm, &st->jp, &st->jm, &st->ep, &st->m, &st->v}) get(p, tot);
+    for (float** p : {&st->y, &st->hx, &st->hxi, &st->sd}) get(p, toty);
+    get(&st->scr, 2 * tot); get(&st->t, (size_t)B);
+    if (rc != PF_OK) { st->reset(e); return rc; }
     st->B = B; st->n = n; st->ny = ny;
     return PF_OK;
 }
@@ -115,15 +98,10 @@ static int fp_begin(pf_engine* e, const pf_degradation* d, const pf_flow_priors_
     if (!(prm->lmbda >= 0.0) || !(prm->eta >= 0.0)) { e->err = "flow_priors: lmbda and eta must not be negative"; return PF_ERR_INVALID; }
     // a plan is built per batch size on first use; what no plan can be built for is refused here, before anything is allocated
     if (B < 1 || B > 65535) { e->err = "flow_priors: batch " + std::to_string(B) + " is not one the engine plans for (1..65535 images)"; return PF_ERR_INVALID; }
-    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_GAUSSIAN_BLUR_ZERO) { e->err = "flow_priors: unknown degradation kind"; return PF_ERR_INVALID; }
     const int C = e->cfg.input_channels, H = e->cfg.input_height;
-    const bool sr = d->kind == PF_DEG_SUPERRESOLUTION || d->kind == PF_DEG_SR_FILTERED;
-    if (sr && (d->sf <= 0 || H % d->sf)) { e->err = "flow_priors: superresolution factor must divide the image size"; return PF_ERR_INVALID; }
-    if ((d->kind == PF_DEG_GAUSSIAN_BLUR || d->kind == PF_DEG_GAUSSIAN_BLUR_ZERO || d->kind == PF_DEG_SR_FILTERED) && (!d->taps || d->ntaps < 1 || d->ntaps > 127)) {
-        e->err = "flow_priors: the filtered operators need 1..127 device taps"; return PF_ERR_INVALID;
-    }
-    if (d->kind == PF_DEG_MASK_INPAINTING && !d->mask) { e->err = "flow_priors: mask inpainting needs a device mask"; return PF_ERR_INVALID; }
-    const int Hy = sr ? H / d->sf : H;
+    int Hy = 0;
+    const int rc = check_operator(e, "flow_priors", d, H, Hy);
+    if (rc != PF_OK) return rc;
     n = (size_t)C * H * H; ny = (size_t)C * Hy * Hy;
     if (n % 4) { e->err = "flow_priors: C*H*W must be a multiple of 4"; return PF_ERR_INVALID; }
     return PF_OK;

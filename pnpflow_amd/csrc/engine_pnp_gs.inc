@@ -17,58 +17,29 @@ struct PnpGsState {
     float *tab = nullptr, *cur = nullptr, *coef = nullptr; // [max_iter] level table, [B] level of this iteration, [B] lr / sigma^2
     int* iter = nullptr;
     double* dbl = nullptr;                                 // [0] alpha, [1] |H(x) - y|^2 carried, [2] g, [8 ..) 3 x PNPGS_MAX_PARTS partials, then [max_iter][2] (gap, threshold)
-    int64_t bytes = 0;
+    DevBufs mem;
     struct Key { const void* plan; int kind, half, sf, ntaps; const void* mask; const void* taps; int B, algo, noise_model, skip, max_iter; float grad_coef; };
-    Key key{}; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
+    static_assert(sizeof(Key) == 3 * sizeof(void*) + 10 * sizeof(int), "PnpGsState::Key is compared with memcmp: it must have no padding bytes");
+    CachedGraph graph;
+    void reset(pf_engine* e) { graph.drop(e); /* its nodes point into the buffers */ mem.release(e); *this = PnpGsState{}; }
     double* part(int i) const { return dbl + 8 + (size_t)i * PNPGS_MAX_PARTS; }
     double* log() const { return dbl + 8 + (size_t)3 * PNPGS_MAX_PARTS; }
 };
-
-static void drop_pnpgs_graph(pf_engine* e) {
-    PnpGsState* st = e->pnpgs;
-    if (!st) return;
-    if (st->exec) hipGraphExecDestroy(st->exec);
-    if (st->graph) hipGraphDestroy(st->graph);
-    st->exec = nullptr; st->graph = nullptr; st->key = PnpGsState::Key{};
-    e->held_pnpgs_plan = nullptr;
-}
-
-static void free_pnpgs_bufs(pf_engine* e) {
-    PnpGsState* st = e->pnpgs;
-    drop_pnpgs_graph(e);        // its nodes point into the buffers
-    for (void* p : {(void*)st->x, (void*)st->z, (void*)st->N, (void*)st->r, (void*)st->JN, (void*)st->rhs, (void*)st->hadj, (void*)st->y, (void*)st->hx,
-                    (void*)st->scr, (void*)st->pw, (void*)st->tab, (void*)st->cur, (void*)st->coef, (void*)st->iter, (void*)st->dbl})
-        if (p) hipFree(p);
-    e->bytes -= st->bytes;
-    *st = PnpGsState{};
-}
-
-static void free_pnpgs(pf_engine* e) {
-    if (!e->pnpgs) return;
-    free_pnpgs_bufs(e);
-    delete e->pnpgs;
-    e->pnpgs = nullptr;
-}
 
 static int ensure_pnpgs(pf_engine* e, int B, size_t n, size_t ny, int max_iter) {
     if (!e->pnpgs) e->pnpgs = new PnpGsState();
     PnpGsState* st = e->pnpgs;
     if (st->B == B && st->n == n && st->ny == ny && st->max_iter >= max_iter) return PF_OK;
-    free_pnpgs_bufs(e);
+    st->reset(e);
     const size_t tot = (size_t)B * n, toty = (size_t)B * ny;
     const int H = e->cfg.input_height;
-    int64_t by = 0; int rc = PF_OK;
-    for (float** p : {&st->x, &st->z, &st->N, &st->r, &st->JN, &st->rhs, &st->hadj}) if (rc == PF_OK) rc = dflow_alloc(e, p, tot, by);
-    for (float** p : {&st->y, &st->hx}) if (rc == PF_OK) rc = dflow_alloc(e, p, toty, by);
-    if (rc == PF_OK) rc = dflow_alloc(e, &st->scr, 2 * tot, by);
-    if (rc == PF_OK) rc = dflow_alloc(e, &st->pw, (size_t)2 * H, by);
-    if (rc == PF_OK) rc = dflow_alloc(e, &st->tab, (size_t)max_iter, by);
-    if (rc == PF_OK) rc = dflow_alloc(e, &st->cur, (size_t)B, by);
-    if (rc == PF_OK) rc = dflow_alloc(e, &st->coef, (size_t)B, by);
-    if (rc == PF_OK) rc = dflow_alloc(e, (float**)&st->iter, 64, by);
-    if (rc == PF_OK) rc = dflow_alloc(e, (float**)&st->dbl, 2 * ((size_t)8 + 3 * PNPGS_MAX_PARTS + 2 * (size_t)max_iter), by);
-    st->bytes = by; e->bytes += by;
-    if (rc != PF_OK) { free_pnpgs_bufs(e); return rc; }
+    int rc = PF_OK;
+    auto get = [&](auto** p, size_t count) { if (rc == PF_OK) rc = st->mem.alloc4(e, p, count); };
+    for (float** p : {&st->x, &st->z, &st->N, &st->r, &st->JN, &st->rhs, &st->hadj}) get(p, tot);
+    for (float** p : {&st->y, &st->hx}) get(p, toty);
+    get(&st->scr, 2 * tot); get(&st->pw, (size_t)2 * H); get(&st->tab, (size_t)max_iter); get(&st->cur, (size_t)B); get(&st->coef, (size_t)B);
+    get(&st->iter, 64); get(&st->dbl, 2 * ((size_t)8 + 3 * PNPGS_MAX_PARTS + 2 * (size_t)max_iter));
+    if (rc != PF_OK) { st->reset(e); return rc; }
     st->B = B; st->n = n; st->ny = ny; st->max_iter = max_iter;
     return PF_OK;
 }
@@ -121,15 +92,6 @@ static int enqueue_pnpgs_iteration(pf_engine* e, Plan* pr, const DegView& dv, co
     }
     hipLaunchKernelGGL(bump_iter_kernel, dim3(1), dim3(64), 0, s, st->iter);
     GS_LAUNCH("iteration", hipGetLastError());
-    return PF_OK;
-}
-
-static int pnpgs_stream(pf_engine* e, bool need_graph_stream, hipStream_t& s) {
-    if (need_graph_stream && s == nullptr) {
-        if (!e->work_stream) HIPCHK(e, hipStreamCreateWithFlags(&e->work_stream, hipStreamDefault));
-        HIPCHK(e, hipStreamSynchronize(nullptr));
-        s = e->work_stream;
-    }
     return PF_OK;
 }
 
@@ -197,7 +159,7 @@ int pf_pnp_gs_restore(pf_engine* e, const pf_degradation* d, const pf_pnp_gs_par
     USE_DEVICE(e);
     hipStream_t s = (hipStream_t)stream;
     const bool can_graph = prm->use_graph && !e->profile;
-    int rc = pnpgs_stream(e, can_graph, s);
+    int rc = graph_stream(e, can_graph, s);
     if (rc != PF_OK) return rc;
     if ((rc = ensure_pnpgs(e, B, n, ny, prm->max_iter)) != PF_OK) return rc;
     PnpGsState* st = e->pnpgs;
@@ -225,29 +187,17 @@ int pf_pnp_gs_restore(pf_engine* e, const pf_degradation* d, const pf_pnp_gs_par
     }
     HIPCHK(e, hipStreamSynchronize(s));      // the host table may go away after return
 
-    static_assert(sizeof(PnpGsState::Key) == 3 * sizeof(void*) + 10 * sizeof(int), "PnpGsState::Key is compared with memcmp: it must have no padding bytes");
     PnpGsState::Key key; memset(&key, 0, sizeof key);
     key.plan = pr; key.kind = dv.kind; key.half = dv.half; key.sf = dv.sf; key.ntaps = dv.ntaps; key.mask = dv.mask; key.taps = dv.taps; key.B = B;
     key.algo = prm->algo; key.noise_model = prm->noise_model; key.skip = prm->skip_grad_step ? 1 : 0; key.max_iter = st->max_iter; key.grad_coef = prm->grad_coef;
-    if (st->exec && memcmp(&key, &st->key, sizeof key) != 0) drop_pnpgs_graph(e);
+    st->graph.keep_for(e, key);
     for (int it = first; it < prm->stop; ++it) {
         // pnp_gs.py:153: the last iteration of hqs random_inpainting leaves x as it is - its denoiser evaluation is dead and skipped
         const bool dead = prm->algo == 1 && it == prm->max_iter - 1;
         if (!dead) {
-            if (can_graph && (it > first || st->exec)) {
-                if (!st->exec) {
-                    HIPCHK(e, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-                    rc = enqueue_pnpgs_iteration(e, pr, dv, prm, s);
-                    hipGraph_t g = nullptr;
-                    hipError_t ce = hipStreamEndCapture(s, &g);
-                    if (rc != PF_OK) { if (g) hipGraphDestroy(g); return rc; }
-                    if (ce != hipSuccess) { e->err = std::string("hipStreamEndCapture: ") + hipGetErrorString(ce); return PF_ERR_HIP; }
-                    st->graph = g;
-                    hipError_t ie = hipGraphInstantiate(&st->exec, st->graph, nullptr, nullptr, 0);
-                    if (ie != hipSuccess) { drop_pnpgs_graph(e); e->err = std::string("hipGraphInstantiate: ") + hipGetErrorString(ie); return PF_ERR_HIP; }
-                    st->key = key; e->held_pnpgs_plan = pr;
-                }
-                HIPCHK(e, hipGraphLaunch(st->exec, s));
+            if (can_graph && (it > first || st->graph.live())) {
+                if (!st->graph.live() && (rc = st->graph.capture(e, s, key, {pr}, [&] { return enqueue_pnpgs_iteration(e, pr, dv, prm, s); })) != PF_OK) return rc;
+                if ((rc = st->graph.launch(e, s)) != PF_OK) return rc;
             } else {
                 if ((rc = enqueue_pnpgs_iteration(e, pr, dv, prm, s)) != PF_OK) return rc;
             }

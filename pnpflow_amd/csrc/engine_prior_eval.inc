@@ -11,48 +11,32 @@ struct PriorEvalState {
     float *y = nullptr, *y1 = nullptr, *stage = nullptr, *k[7] = {}, *g = nullptr;     // [B n]; g: J^T eps (and pf_flow_divergence's v when v_out is NULL: stage)
     float* t = nullptr;                                                               // [B]
     double* dbl = nullptr;       // [7][B] stage divergences, [2][B] logp, [B][64] per-image partials, [64] norm partials, [2] norm sums
-    int64_t bytes = 0;
+    DevBufs mem;
     double* kdiv(int j) const { return dbl + (size_t)j * B; }
     double* logp(int i) const { return dbl + (size_t)(7 + i) * B; }
     double* part() const { return dbl + (size_t)9 * B; }
     double* npart() const { return dbl + (size_t)(9 + 64) * B; }
     double* red() const { return npart() + 64; }
+    void reset(pf_engine* e) { mem.release(e); *this = PriorEvalState{}; }
 };
-
-static void free_prior_bufs(pf_engine* e) {
-    PriorEvalState* st = e->prior;
-    for (void* p : {(void*)st->y, (void*)st->y1, (void*)st->stage, (void*)st->g, (void*)st->t, (void*)st->dbl}) if (p) hipFree(p);
-    for (float* k : st->k) if (k) hipFree(k);
-    e->bytes -= st->bytes;
-    *st = PriorEvalState{};
-}
-
-static void free_prior(pf_engine* e) {
-    if (!e->prior) return;
-    free_prior_bufs(e);
-    delete e->prior;
-    e->prior = nullptr;
-}
 
 // `solve`: the state and stage buffers of the likelihood solve as well (pf_flow_divergence and the sampler need g, stage, t and the doubles only)
 static int ensure_prior(pf_engine* e, int B, size_t n, bool solve) {
     if (!e->prior) e->prior = new PriorEvalState();
     PriorEvalState* st = e->prior;
     if (st->B == B && st->n == n && (!solve || st->y)) return PF_OK;
-    if (st->B != B || st->n != n) free_prior_bufs(e);
+    if (st->B != B || st->n != n) st->reset(e);
     const size_t tot = (size_t)B * n;
-    int64_t by = 0; int rc = PF_OK;
+    int rc = PF_OK;
+    auto get = [&](auto** p, size_t count) { if (rc == PF_OK) rc = st->mem.alloc4(e, p, count); };
     if (!st->g) {
-        for (float** p : {&st->g, &st->stage}) if (rc == PF_OK) rc = dflow_alloc(e, p, tot, by);
-        if (rc == PF_OK) rc = dflow_alloc(e, &st->t, (size_t)B, by);
-        if (rc == PF_OK) rc = dflow_alloc(e, (float**)&st->dbl, 2 * ((size_t)(9 + 64) * B + 64 + 2), by);
+        get(&st->g, tot); get(&st->stage, tot); get(&st->t, (size_t)B); get(&st->dbl, 2 * ((size_t)(9 + 64) * B + 64 + 2));
     }
-    if (solve && !st->y) {
-        for (float** p : {&st->y, &st->y1}) if (rc == PF_OK) rc = dflow_alloc(e, p, tot, by);
-        for (float*& k : st->k) if (rc == PF_OK) rc = dflow_alloc(e, &k, tot, by);
+    if (solve && !st->y) {       // added to the live set
+        get(&st->y, tot); get(&st->y1, tot);
+        for (float*& k : st->k) get(&k, tot);
     }
-    st->bytes += by; e->bytes += by;
-    if (rc != PF_OK) { free_prior_bufs(e); return rc; }
+    if (rc != PF_OK) { st->reset(e); return rc; }
     st->B = B; st->n = n;
     return PF_OK;
 }
