@@ -26,6 +26,10 @@ class Degradation:
     def H_adj(self, x):
         raise NotImplementedError()
 
+    def out_side(self, side):
+        """Side of H's output for an input of side `side`: the two superresolution kinds decimate by sf."""
+        return side // (getattr(self, "sf", 1) if self.kind in (_lib.PF_DEG_SUPERRESOLUTION, _lib.PF_DEG_SR_FILTERED) else 1)
+
     # -- engine side -----------------------------------------------------------------------
     def descriptor(self, B, H, W, device):
         raise NotImplementedError()
@@ -41,8 +45,7 @@ class Degradation:
         if adjoint:
             out = torch.empty((B, Cc, Hf, Wf), dtype=torch.float32, device=x.device)
         else:
-            sf = getattr(self, "sf", 1) if self.kind in (_lib.PF_DEG_SUPERRESOLUTION, _lib.PF_DEG_SR_FILTERED) else 1
-            out = torch.empty((B, Cc, Hf // sf, Wf // sf), dtype=torch.float32, device=x.device)
+            out = torch.empty((B, Cc, self.out_side(Hf), self.out_side(Wf)), dtype=torch.float32, device=x.device)
         if B == 0:
             return out          # an empty shard (global batch smaller than the number of ranks): nothing to launch
         n_scr = {_lib.PF_DEG_GAUSSIAN_BLUR: 1, _lib.PF_DEG_GAUSSIAN_BLUR_ZERO: 1, _lib.PF_DEG_SR_FILTERED: 2}.get(self.kind, 0)

@@ -14,7 +14,6 @@ arguments, over the device tensor z.
 from __future__ import annotations
 
 import ctypes as C
-import os
 from time import perf_counter
 
 import numpy as np
@@ -22,34 +21,23 @@ import torch
 
 from .. import _lib
 from .. import parallel
-from .. import utils
+from . import _harness
+from ._harness import Solver
 
 
-class D_FLOW(object):
+class D_FLOW(Solver):
 
     def __init__(self, model, device, args):
-        self.device = device
-        self.args = args
-        self.model = model.to(device)
-        self.method = args.method
-        self.lib = _lib.load()
+        super().__init__(model.to(device), device, args)
+        self.lib = _lib.load()              # here, not on first use: a missing library fails the constructor
         self.use_graph = True               # one hipGraph per T(z) and per closure
         self.init_latent = None             # optional init_latent(batch, x) replacing the dopri5 solve (parity runs)
         self.blend_noise = None             # optional blend_noise(batch, shape) replacing the randn_like(z) of the blend
-        self.measurement_noise = None       # optional measurement_noise(batch, noisy) replacing the torch.manual_seed(batch) draw
-        self.measurement_noise_source = getattr(args, "measurement_noise", "cpu")      # "cpu" | "device" (the reference's: d_flow.py:78-80)
         self.dopri5_max_steps = 1000        # attempts (accepted + rejected) before the latent initialisation fails loudly
         self.last_dopri5_stats = None
-        self.last_restored = None
         self.closure_calls = 0
 
-    def model_forward(self, x, t):
-        if self.args.model == "ot":
-            return self.model(x, t)
-        if self.args.model == "rectified":        # d_flow.py:29-34: model_fn(x, t * 999)
-            return self.model(x.type(torch.float), t * 999)
-        raise NotImplementedError("only the 'ot' U-Net and the 'rectified' NCSN++ net are implemented")
-
+    # model_forward (d_flow.py:29-34) is Solver's
     def gaussian(self, img):
         if img.ndim != 4:
             raise RuntimeError(f"Expected input `img` to be an 4D tensor, but got {img.shape}")
@@ -61,10 +49,6 @@ class D_FLOW(object):
         return torch.sqrt((img ** 2).sum([1, 2, 3]))
 
     # ---- engine calls ------------------------------------------------------------------------------------------------------------
-    def _set_time_scale(self):
-        if hasattr(self.model, "set_solver_time_scale"):
-            self.model.set_solver_time_scale(999.0 if self.args.model == "rectified" else 1.0)
-
     def _params(self):
         """Schedule of forward_flow_matching (d_flow.py:41-49) with the reference's own fp32 expressions."""
         steps, start = int(self.args.steps_euler), self.args.start_time
@@ -84,18 +68,13 @@ class D_FLOW(object):
         prm._keep = (t, tm)                # the host tables live as long as the struct
         return prm
 
-    def _check_latent(self, z):
-        Hh = self.model.input_height
-        if z.ndim != 4 or tuple(z.shape[1:]) != (self.model.input_channels, Hh, Hh):
-            raise ValueError(f"latent of shape {tuple(z.shape)} does not match the net's (B, {self.model.input_channels}, {Hh}, {Hh})")
-        if not z.is_cuda:
-            raise _lib.PnpFlowHipError("D_FLOW needs GPU tensors (there is no CPU path)")
+    def _latent(self, z):
+        return _harness.check_image(z, "latent", self.model, "D_FLOW")
 
     def forward_flow_matching(self, z):
         """T(z) (d_flow.py:41-49) on the engine."""
-        self._check_latent(z)
+        z = self._latent(z)
         self._set_time_scale()
-        z = z.detach().contiguous().float()
         out = torch.empty_like(z)
         prm = self._params()
         with _lib.solver_stream():
@@ -105,17 +84,12 @@ class D_FLOW(object):
 
     def value_and_grad(self, z, noisy_img, degradation, lmbda):
         """(loss per image [B], d sum(loss) / dz) of the closure (d_flow.py:110-121) at z."""
-        self._check_latent(z)
+        z = self._latent(z)
         self._set_time_scale()
-        z = z.detach().contiguous().float()
-        y = noisy_img.detach().contiguous().float()
         B, Hh = z.shape[0], self.model.input_height
-        if y.shape[0] != B:
-            raise ValueError(f"measurement batch {y.shape[0]} != latent batch {B}")
-        sf = getattr(degradation, "sf", 1) if degradation.kind in (_lib.PF_DEG_SUPERRESOLUTION, _lib.PF_DEG_SR_FILTERED) else 1
-        if tuple(y.shape[1:]) != (self.model.input_channels, Hh // sf, Hh // sf):
-            raise ValueError(f"measurement of shape {tuple(y.shape)} does not match the operator's output (B, {self.model.input_channels}, "
-                             f"{Hh // sf}, {Hh // sf})")
+        if noisy_img.shape[0] != B:
+            raise ValueError(f"measurement batch {noisy_img.shape[0]} != latent batch {B}")
+        y = _harness.check_measurement(noisy_img, degradation, B, self.model)
         d = degradation.descriptor(B, Hh, Hh, z.device)
         loss = torch.empty(B, dtype=torch.float32, device=z.device)
         grad = torch.empty_like(z)
@@ -128,9 +102,8 @@ class D_FLOW(object):
 
     def inverse_flow_matching(self, z):
         """odeint(cnf, z, [1, 0], rtol = atol = 1e-5, method='dopri5')[-1] (d_flow.py:51-60) on the engine; counts in last_dopri5_stats."""
-        self._check_latent(z)
+        z = self._latent(z)
         self._set_time_scale()
-        z = z.detach().contiguous().float()
         out = torch.empty_like(z)
         prm = _lib.PfDopri5Params()
         prm.t0, prm.t1, prm.rtol, prm.atol, prm.max_steps = 1.0, 0.0, 1e-5, 1e-5, int(self.dopri5_max_steps)
@@ -143,12 +116,9 @@ class D_FLOW(object):
 
     # ---- solver ------------------------------------------------------------------------------------------------------------------
     def solve_ip(self, test_loader, degradation, sigma_noise):
-        rank, world = parallel.rank_world()
-        if world > 1:
-            # LBFGS (one line search over the whole batch) and the dopri5 error norm (one step sequence for the whole batch) couple the
-            # images: a split batch would compute something else
-            raise RuntimeError("d_flow runs on one GPU only: its LBFGS line search and its dopri5 step control couple the whole batch, "
-                               f"so a batch split over {world} ranks would change the result. Run it without torchrun.")
+        # LBFGS (one line search over the whole batch) and the dopri5 error norm (one step sequence for the whole batch) couple the
+        # images: a split batch would compute something else
+        _harness.single_gpu_only(parallel.rank_world()[1], "d_flow runs on one GPU only: its LBFGS line search and its dopri5 step control couple the whole batch")
         H, H_adj = degradation.H, degradation.H_adj
         self.args.sigma_noise = sigma_noise
         loader = iter(test_loader)
@@ -157,10 +127,7 @@ class D_FLOW(object):
             self.args.batch = batch
             noisy_img = H(clean_img.clone().to(self.device))
             G = noisy_img.shape[0]
-            if self.measurement_noise is not None:
-                noise = self.measurement_noise(batch, noisy_img)
-            else:
-                noise = utils.draw_measurement_noise(batch, tuple(noisy_img.shape), 0, G, self.device, self.measurement_noise_source)   # d_flow.py:78-80
+            noise = _harness.measurement_noise(self, batch, noisy_img, tuple(noisy_img.shape), 0, G)   # d_flow.py:78-80: gaussian whatever noise_type says
             noisy_img = noisy_img + noise * sigma_noise
             clean_img = clean_img.to('cpu')
             zshape = (G, self.model.input_channels, self.model.input_height, self.model.input_height)
@@ -180,11 +147,8 @@ class D_FLOW(object):
             z = z.detach().contiguous().requires_grad_(True)
 
             optim_img = torch.optim.LBFGS([z], max_iter=self.args.LBFGS_iter, history_size=100, line_search_fn='strong_wolfe')
-            if self.args.compute_time:
-                torch.cuda.synchronize()
-                time_per_batch = 0
-            if self.args.compute_memory:
-                torch.cuda.reset_peak_memory_stats(self.device)
+            _harness.begin_batch_stats(self)
+            time_per_batch = 0
 
             def closure():
                 optim_img.zero_grad()
@@ -207,28 +171,9 @@ class D_FLOW(object):
             self.last_restored = restored_img
             self.last_latent = z.detach().clone()
 
-            if self.args.compute_memory:
-                utils.save_memory_use({"batch": batch, "max_allocated": torch.cuda.max_memory_allocated(self.device) + self.model.memory_bytes()},
-                                      self.args)
-            if self.args.compute_time:
-                utils.save_time_use({"batch": batch, "time_per_batch": time_per_batch}, self.args)
+            # the reference times step + forward only (d_flow.py:104-127), so the sum is kept here and not by _harness.batch_stats
+            _harness.write_batch_stats(self, batch, time_per_batch)
             if self.args.save_results:
                 restored_img = self.forward_flow_matching(z.detach())
-                utils.save_images(clean_img, noisy_img, restored_img, self.args, H_adj, iter='final')
-                utils.compute_psnr(clean_img, noisy_img, restored_img, self.args, H_adj, iter=iteration)
-                utils.compute_ssim(clean_img, noisy_img, restored_img, self.args, H_adj, iter=iteration)
-                utils.compute_lpips(clean_img, noisy_img, restored_img, self.args, H_adj, iter=iteration)
-        if self.args.save_results:
-            utils.compute_average_psnr(self.args)
-            utils.compute_average_ssim(self.args)
-            utils.compute_average_lpips(self.args)
-        if self.args.compute_memory:
-            utils.compute_average_memory(self.args)
-        if self.args.compute_time:
-            utils.compute_average_time(self.args)
-
-    def run_method(self, data_loaders, degradation, sigma_noise):
-        folder = utils.get_save_path_ip(self.args.dict_cfg_method)
-        self.args.save_path_ip = os.path.join(self.args.save_path, folder)
-        os.makedirs(self.args.save_path_ip, exist_ok=True)
-        self.solve_ip(data_loaders[self.args.eval_split], degradation, sigma_noise)
+                self.write_final(clean_img, noisy_img, restored_img, H_adj, iteration)
+        self.write_averages()

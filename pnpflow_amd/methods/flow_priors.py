@@ -17,46 +17,32 @@ not torch.rand on the device: DESIGN.md section 11.
 from __future__ import annotations
 
 import ctypes as C
-import os
-from time import perf_counter
 
 import torch
 
 from .. import _lib
-from .. import parallel
-from .. import utils
+from . import _harness
+from ._harness import Solver
 
 DEFAULT_FD_STEP = 3e-3          # the step with the smallest measured error of the engine's trace gradient
 NOISE_MODELS = {"gaussian": 0, "laplace": 1}
 
 
-class FLOW_PRIORS(object):
+class FLOW_PRIORS(Solver):
 
     def __init__(self, model, device, args):
-        self.device = device
-        self.args = args
-        self.model = model.to(device)
-        self.method = args.method
+        super().__init__(model.to(device), device, args)       # the library is loaded on the first engine call
         self.N = args.N
-        self.lib = None                     # loaded on the first engine call
         self.fd_step = float(getattr(args, "fd_step", DEFAULT_FD_STEP))
         self.probes = None                  # optional probes(batch, first, stop, K, shape) -> (stop - first) * K injected probes (parity runs)
-        self.measurement_noise = None       # optional measurement_noise(batch, noisy) replacing the seeded draw (unit scale)
         self.init_noise = None              # optional init_noise(batch, shape) replacing the torch.randn of x_init
-        self.measurement_noise_source = getattr(args, "measurement_noise", "cpu")
-        self.last_restored = None
 
-    def model_forward(self, x, t):
-        if self.args.model == "ot":
-            return self.model(x, t)
-        if self.args.model == "rectified":        # flow_priors.py:22-25: model_fn(x, t * 999)
-            return self.model(x.type(torch.float), t * 999)
-        raise NotImplementedError("only the 'ot' U-Net and the 'rectified' NCSN++ net are implemented")
+    # model_forward (flow_priors.py:22-25) is Solver's
 
     # ---- engine calls ------------------------------------------------------------------------------------------------------------
     def _time_scale(self):
         if self.args.model not in ("ot", "rectified"):
-            raise NotImplementedError("only the 'ot' U-Net and the 'rectified' NCSN++ net are implemented")
+            raise self._coupling_error()
         return 999.0 if self.args.model == "rectified" else 1.0
 
     def _params(self, batch=0, first=0, stop=0):
@@ -71,29 +57,15 @@ class FLOW_PRIORS(object):
         return prm
 
     def _check(self, x, what):
-        Hh = self.model.input_height
-        if x.ndim != 4 or tuple(x.shape[1:]) != (self.model.input_channels, Hh, Hh):
-            raise ValueError(f"{what} of shape {tuple(x.shape)} does not match the net's (B, {self.model.input_channels}, {Hh}, {Hh})")
-        if not x.is_cuda:
-            raise _lib.PnpFlowHipError("FLOW_PRIORS needs GPU tensors (there is no CPU path)")
-        return x.detach().contiguous().float()
-
-    def _check_measurement(self, y, degradation, B):
-        Hh = self.model.input_height
-        sf = getattr(degradation, "sf", 1) if degradation.kind in (_lib.PF_DEG_SUPERRESOLUTION, _lib.PF_DEG_SR_FILTERED) else 1
-        if tuple(y.shape) != (B, self.model.input_channels, Hh // sf, Hh // sf):
-            raise ValueError(f"measurement of shape {tuple(y.shape)} does not match the operator's output ({B}, {self.model.input_channels}, "
-                             f"{Hh // sf}, {Hh // sf})")
-        return y.detach().contiguous().float()
+        return _harness.check_image(x, what, self.model, "FLOW_PRIORS")
 
     def gradient(self, x, x_init, noisy_img, degradation, eps, iteration):
         """(g, g_data, g_trace, pred) of one inner step of outer iteration `iteration` at x with the probe eps (pf_flow_priors_grad)."""
         x, x_init, eps = self._check(x, "x"), self._check(x_init, "x_init"), self._check(eps, "eps")
         B, Hh = x.shape[0], self.model.input_height
-        y = self._check_measurement(noisy_img, degradation, B)
+        y = _harness.check_measurement(noisy_img, degradation, B, self.model)
         d = degradation.descriptor(B, Hh, Hh, x.device)
         prm = self._params()
-        self.lib = self.lib or _lib.load()
         outs = [torch.empty_like(x) for _ in range(4)]
         _lib.check(self.lib.pf_flow_priors_grad(self.model.handle, C.byref(d), C.byref(prm), x.data_ptr(), x_init.data_ptr(), y.data_ptr(), eps.data_ptr(),
                                                 int(iteration), *[o.data_ptr() for o in outs], B, _lib.current_stream_ptr()),
@@ -104,7 +76,7 @@ class FLOW_PRIORS(object):
         """Outer iterations [first, stop) (stop 0: N) of the loop for one batch (pf_flow_priors_restore); x0: the iterate entering `first` > 0."""
         x_init = self._check(x_init, "x_init")
         B, Hh = x_init.shape[0], self.model.input_height
-        y = self._check_measurement(noisy_img, degradation, B)
+        y = _harness.check_measurement(noisy_img, degradation, B, self.model)
         d = degradation.descriptor(B, Hh, Hh, x_init.device)
         prm = self._params(batch, first, stop)
         if first > 0 and x0 is None:
@@ -115,7 +87,6 @@ class FLOW_PRIORS(object):
             n_steps = ((stop or int(self.args.N)) - first) * int(self.args.K)
             if probes.numel() != n_steps * x_init.numel() or not probes.is_cuda:
                 raise ValueError(f"probes must hold {n_steps} device tensors of shape {tuple(x_init.shape)}")
-        self.lib = self.lib or _lib.load()
         with _lib.solver_stream():
             _lib.check(self.lib.pf_flow_priors_restore(self.model.handle, C.byref(d), C.byref(prm), y.data_ptr(), x_init.data_ptr(),
                                                        probes.data_ptr() if probes is not None else None, x.data_ptr(), B, _lib.current_stream_ptr()),
@@ -124,10 +95,7 @@ class FLOW_PRIORS(object):
 
     # ---- solver ------------------------------------------------------------------------------------------------------------------
     def solve_ip(self, test_loader, degradation, sigma_noise):
-        world = max(parallel.rank_world()[1], int(os.environ.get("WORLD_SIZE", "1")))
-        if world > 1:
-            raise RuntimeError("flow_priors runs on one GPU only: multi-GPU sharding of this solver is not built, "
-                               f"so a batch split over {world} ranks would change the result. Run it without torchrun.")
+        _harness.single_gpu_only(_harness.env_world(), "flow_priors runs on one GPU only: multi-GPU sharding of this solver is not built")
         if self.args.noise_type not in NOISE_MODELS:
             raise ValueError('Noise type not supported')
         self._time_scale()
@@ -139,51 +107,17 @@ class FLOW_PRIORS(object):
             self.args.batch = batch
             noisy_img = H(clean_img.clone().to(self.device))
             G = noisy_img.shape[0]
-            if self.measurement_noise is not None:
-                noise = self.measurement_noise(batch, noisy_img)
-            elif self.args.noise_type == 'gaussian':
-                noise = utils.draw_measurement_noise(batch, tuple(noisy_img.shape), 0, G, self.device, self.measurement_noise_source)   # flow_priors.py:44-45
-            else:
-                # flow_priors.py:48-50: the laplace draw is not re-seeded by the reference
-                noise = torch.distributions.laplace.Laplace(torch.zeros(tuple(noisy_img.shape)), torch.ones(tuple(noisy_img.shape))).sample().to(self.device)
+            # flow_priors.py:44-50: the laplace draw is not re-seeded by the reference
+            noise = _harness.measurement_noise(self, batch, noisy_img, tuple(noisy_img.shape), 0, G, self.args.noise_type)
             noisy_img = noisy_img + noise * sigma_noise
             clean_img = clean_img.to('cpu')
             shape = (G, self.model.input_channels, self.model.input_height, self.model.input_height)
             # flow_priors.py:57-58: x_init ~ N(0, I), the draw after the measurement noise on the CPU generator
             x_init = (self.init_noise(batch, shape) if self.init_noise is not None else torch.randn(shape)).to(self.device).float()
 
-            if self.args.compute_time:
-                torch.cuda.synchronize()
-                t0 = perf_counter()
-            if self.args.compute_memory:
-                torch.cuda.reset_peak_memory_stats(self.device)
-            probes = self.probes(batch, 0, int(self.args.N), int(self.args.K), shape) if self.probes is not None else None
-            restored_img = self.restore_batch(noisy_img, x_init, degradation, batch=batch, probes=probes)
-            self.last_restored = restored_img
-            iteration = int(self.args.N) - 1
-
-            if self.args.compute_memory:
-                utils.save_memory_use({"batch": batch, "max_allocated": torch.cuda.max_memory_allocated(self.device) + self.model.memory_bytes()},
-                                      self.args)
-            if self.args.compute_time:
-                torch.cuda.synchronize()
-                utils.save_time_use({"batch": batch, "time_per_batch": perf_counter() - t0}, self.args)
-            if self.args.save_results:
-                utils.save_images(clean_img, noisy_img, restored_img, self.args, H_adj, iter='final')
-                utils.compute_psnr(clean_img, noisy_img, restored_img, self.args, H_adj, iter=iteration)
-                utils.compute_ssim(clean_img, noisy_img, restored_img, self.args, H_adj, iter=iteration)
-                utils.compute_lpips(clean_img, noisy_img, restored_img, self.args, H_adj, iter=iteration)
-        if self.args.save_results:
-            utils.compute_average_psnr(self.args)
-            utils.compute_average_ssim(self.args)
-            utils.compute_average_lpips(self.args)
-        if self.args.compute_memory:
-            utils.compute_average_memory(self.args)
-        if self.args.compute_time:
-            utils.compute_average_time(self.args)
-
-    def run_method(self, data_loaders, degradation, sigma_noise):
-        folder = utils.get_save_path_ip(self.args.dict_cfg_method)
-        self.args.save_path_ip = os.path.join(self.args.save_path, folder)
-        os.makedirs(self.args.save_path_ip, exist_ok=True)
-        self.solve_ip(data_loaders[self.args.eval_split], degradation, sigma_noise)
+            with _harness.batch_stats(self, batch):
+                probes = self.probes(batch, 0, int(self.args.N), int(self.args.K), shape) if self.probes is not None else None
+                restored_img = self.restore_batch(noisy_img, x_init, degradation, batch=batch, probes=probes)
+                self.last_restored = restored_img
+            self.write_final(clean_img, noisy_img, restored_img, H_adj, int(self.args.N) - 1)
+        self.write_averages()

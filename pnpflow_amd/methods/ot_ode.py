@@ -9,7 +9,6 @@ update are HIP pointwise kernels (pf_ot_ode_vec / pf_ot_ode_update).
 from __future__ import annotations
 
 import ctypes as C
-import os
 from time import perf_counter
 
 import numpy as np
@@ -17,32 +16,20 @@ import torch
 
 from .. import _lib
 from .. import parallel
-from .. import utils
+from . import _harness
+from ._harness import IterCallback, Solver
 
 
-class OT_ODE(object):
+class OT_ODE(Solver):
 
     def __init__(self, model, device, args):
-        self.device = device
-        self.args = args
-        self.model = model.to(device)
-        self.method = args.method
-        self.lib = _lib.load()
+        super().__init__(model.to(device), device, args)
+        self.lib = _lib.load()          # here, not on first use: a missing library fails the constructor
         self.use_graph = True           # one hipGraph per Euler step
-        self.last_callback_seconds = 0.0
         self.init_noise = None          # optional override of the randn_like in `initialization` (parity runs)
-        self.measurement_noise = None   # optional override of the torch.manual_seed(batch) draw
-        self.measurement_noise_source = getattr(args, "measurement_noise", "cpu")      # "cpu" | "device" (the reference's: ot_ode.py:44-45), see PNP_FLOW
-        self.last_restored = None
         self.last_krylov_iterations = 0   # Krylov iterations the engine loop enqueued in the last restore_batch (zero-boundary blur only)
 
-    def model_forward(self, x, t):
-        if self.args.model == "ot":
-            return self.model(x, t)
-        if self.args.model == "rectified":        # ot_ode.py:21-25: model_fn(x, t * 999)
-            return self.model(x.type(torch.float), t * 999)
-        raise NotImplementedError("only the 'ot' U-Net and the 'rectified' NCSN++ net are implemented")
-
+    # model_forward (ot_ode.py:21-25) is Solver's
     def initialization(self, noisy_img, t0):
         noise = self.init_noise if self.init_noise is not None else torch.randn(noisy_img.shape).to(noisy_img.device)
         return t0 * noisy_img + (1 - t0) * noise
@@ -68,8 +55,7 @@ class OT_ODE(object):
         iterations in `cb_iterations` (None = every iteration)."""
         args = self.args
         problem = args.problem
-        if hasattr(self.model, "set_solver_time_scale"):
-            self.model.set_solver_time_scale(999.0 if args.model == "rectified" else 1.0)       # model_fn(x, t * 999), ot_ode.py:21-25
+        self._set_time_scale()          # model_fn(x, t * 999), ot_ode.py:21-25
         # the zero-boundary blur has no closed-form solve either, but it is a table entry of main.py (problem gaussian_deblurring): the engine loop runs
         # the reference's generic branch for it with the batched GMRES on the device (pf_krylov_solve inside pf_ot_ode_restore)
         krylov = getattr(degradation, "kind", None) == _lib.PF_DEG_GAUSSIAN_BLUR_ZERO
@@ -101,30 +87,13 @@ class OT_ODE(object):
         prm.sigma2 = float(np.float32(sigma_noise) ** 2) if problem == "superresolution" else float(sigma_noise ** 2)
         prm.delta = float(delta)
         prm.use_graph = 1 if self.use_graph else 0
-        holder = {"err": None}
-        self.last_callback_seconds = 0.0
-        if iter_cb is not None:
-            def _cb(it, user):
-                t_cb = perf_counter()
-                try:
-                    if holder["err"] is None:
-                        iter_cb(it, x)
-                except BaseException as exc:      # must not unwind through the C frames: re-raised below
-                    holder["err"] = exc
-                self.last_callback_seconds += perf_counter() - t_cb
-            cb = _lib.ITER_CB(_cb)
-            if cb_iterations is not None:
-                mask = np.zeros(steps, dtype=np.uint8)
-                mask[[i for i in cb_iterations if 0 <= i < steps]] = 1
-                holder["mask"] = mask
-                prm.host_cb_mask = mask.ctypes.data
-        else:
-            cb = C.cast(None, _lib.ITER_CB)
+        call = IterCallback(iter_cb, steps, cb_iterations)
+        call.attach(prm); call.bind(x)
         with _lib.solver_stream():       # engine launches and metric callbacks on ONE stream (a real one: graph capture)
             _lib.check(self.lib.pf_ot_ode_restore(self.model.handle, C.byref(d), C.byref(prm), y.data_ptr(), x.data_ptr(), B,
-                                                  _lib.current_stream_ptr(), cb, None), self.model.handle, "pf_ot_ode_restore")
-        if holder["err"] is not None:
-            raise holder["err"]
+                                                  _lib.current_stream_ptr(), call.cb, None), self.model.handle, "pf_ot_ode_restore")
+        self.last_callback_seconds = call.seconds
+        call.reraise()
         self.last_krylov_iterations = int(self.lib.pf_ot_ode_krylov_iterations(self.model.handle))      # 0 unless the engine's Krylov branch ran
         return x
 
@@ -197,24 +166,15 @@ class OT_ODE(object):
         self.args.sigma_noise = sigma_noise
         H, H_adj = degradation.H, degradation.H_adj
         steps = self.args.steps_ode
-        # multi-GPU: every rank restores its slice [lo, hi) of each batch; global draws sliced, metrics gathered (parallel.py)
-        rank, world = parallel.rank_world()
+        world = parallel.rank_world()[1]
         loader = iter(test_loader)
         for batch in range(self.args.max_batch):
             (clean_img, labels) = next(loader)
             self.args.batch = batch
-            G = clean_img.shape[0]
-            lo, hi = parallel.shard_range(G, rank, world)
-            if world > 1:
-                clean_img = clean_img[lo:hi]
-                if hasattr(degradation, "set_shard"):
-                    degradation.set_shard(G, lo)
+            clean_img, G, lo, hi = _harness.shard_of_batch(clean_img, degradation)       # multi-GPU: this rank's slice [lo, hi) of the batch
             noisy_img = H(clean_img.clone().to(self.device))
             gshape = (G,) + tuple(noisy_img.shape[1:])
-            if self.measurement_noise is not None:
-                noise = self.measurement_noise(batch, noisy_img)
-            else:
-                noise = utils.draw_measurement_noise(batch, gshape, lo, hi, self.device, self.measurement_noise_source)      # ot_ode.py:44-45
+            noise = _harness.measurement_noise(self, batch, noisy_img, gshape, lo, hi)      # ot_ode.py:44-45: gaussian whatever noise_type says
             noisy_img = noisy_img + noise * sigma_noise
             clean_img = clean_img.to('cpu')
             if (world > 1 or self.measurement_noise_source == "device") and self.init_noise is None:
@@ -227,15 +187,9 @@ class OT_ODE(object):
                     init = torch.randn(full, dtype=torch.float32)[lo:hi].to(self.device)
             else:
                 init = None
-            if self.args.compute_time:
-                torch.cuda.synchronize(); t0 = perf_counter()
-            if self.args.compute_memory:
-                torch.cuda.reset_peak_memory_stats(self.device)
 
             def on_iter(iteration, x):
-                utils.compute_psnr(clean_img, noisy_img, x.detach().clone(), self.args, H_adj, iter=iteration)
-                utils.compute_ssim(clean_img, noisy_img, x.detach().clone(), self.args, H_adj, iter=iteration)
-                utils.compute_lpips(clean_img, noisy_img, x.detach().clone(), self.args, H_adj, iter=iteration)
+                self.write_metrics(clean_img, noisy_img, x, H_adj, iteration)
 
             # the reference's logging iterations (ot_ode.py:149-150): the host is not involved on any other iteration
             log_its = [it for it in range(int(steps * self.args.start_time), int(steps))
@@ -245,36 +199,14 @@ class OT_ODE(object):
             if init is not None:
                 self.init_noise = init
             try:
-                x = self.restore_batch(noisy_img, degradation, sigma_noise, iter_cb=on_iter if self.args.save_results else None,
-                                       cb_iterations=log_its)
+                with _harness.batch_stats(self, batch):
+                    x = self.restore_batch(noisy_img, degradation, sigma_noise, iter_cb=on_iter if self.args.save_results else None,
+                                           cb_iterations=log_its)
             finally:
                 self.init_noise = saved_init
             self.last_restored = x
-            if self.args.compute_memory:
-                utils.save_memory_use({"batch": batch, "max_allocated": torch.cuda.max_memory_allocated(self.device) + self.model.memory_bytes()},
-                                      self.args)
-            if self.args.compute_time:
-                torch.cuda.synchronize()
-                utils.save_time_use({"batch": batch, "time_per_batch": perf_counter() - t0 - self.last_callback_seconds}, self.args)
-            if self.args.save_results:
-                utils.save_images(clean_img, noisy_img, x.detach().clone(), self.args, H_adj, iter='final')
-                utils.compute_psnr(clean_img, noisy_img, x.detach().clone(), self.args, H_adj, iter=int(steps) - 1)
-                utils.compute_ssim(clean_img, noisy_img, x.detach().clone(), self.args, H_adj, iter=int(steps) - 1)
-                utils.compute_lpips(clean_img, noisy_img, x.detach().clone(), self.args, H_adj, iter=int(steps) - 1)
-        if self.args.save_results:
-            utils.compute_average_psnr(self.args)
-            utils.compute_average_ssim(self.args)
-            utils.compute_average_lpips(self.args)
-        if self.args.compute_memory:
-            utils.compute_average_memory(self.args)
-        if self.args.compute_time:
-            utils.compute_average_time(self.args)
+            self.write_final(clean_img, noisy_img, x, H_adj, int(steps) - 1)
+        self.write_averages()
 
     def should_save_image(self, iteration, steps):
         return iteration % (steps // 10) == 0
-
-    def run_method(self, data_loaders, degradation, sigma_noise):
-        folder = utils.get_save_path_ip(self.args.dict_cfg_method)
-        self.args.save_path_ip = os.path.join(self.args.save_path, folder)
-        os.makedirs(self.args.save_path_ip, exist_ok=True)
-        self.solve_ip(data_loaders[self.args.eval_split], degradation, sigma_noise)

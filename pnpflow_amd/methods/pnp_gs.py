@@ -15,54 +15,30 @@ per iteration, replayed as one hipGraph; alpha lives on the device.
 from __future__ import annotations
 
 import ctypes as C
-import os
-from time import perf_counter
 
 import numpy as np
 import torch
 
 from .. import _lib
-from .. import parallel
-from .. import utils
+from . import _harness
+from ._harness import IterCallback, Solver
 
 SUPPORTED = "algo pgd (any problem, gaussian or laplace noise), algo hqs with problem random_inpainting, algo hqs with problem gaussian_deblurring_FFT"
 
 
-class PROX_PNP(object):
+class PROX_PNP(Solver):
 
     def __init__(self, model, device, args):
-        self.device = device
-        self.args = args
-        self.model = model
-        self.method = args.method
-        self._lib = None
+        super().__init__(model, device, args)       # the library is loaded on the first engine call
         self.use_graph = True               # one hipGraph per iteration
-        self.measurement_noise = None       # optional measurement_noise(batch, noisy) replacing the seeded draw (unit scale)
-        self.measurement_noise_source = getattr(args, "measurement_noise", "cpu")      # "cpu" | "device" (the reference's: pnp_gs.py:105-106)
-        self.last_restored = None
         self.last_alpha = None              # alpha after the last restore_batch (hqs deblurring decays it)
         self.last_gap_log = None            # hqs deblurring: [max_iter, 2] (gap, threshold) of the iterations the last restore_batch ran
-        self.last_callback_seconds = 0.0
 
-    @property
-    def lib(self):
-        if self._lib is None:
-            self._lib = _lib.load()
-        return self._lib
-
-    # ---- the reference's method surface ----------------------------------------------------------------------------------------
+    # ---- the reference's method surface (grad_datafit, pnp_gs.py:23-30, is Solver's) -------------------------------------------
     def model_forward(self, x):
         sigma = torch.ones(len(x), device=self.device) * self.args.sigma_noise
         if self.args.model == "gradient_step":
             return self.model(x, sigma)
-
-    def grad_datafit(self, x, y, H, H_adj):
-        if self.args.noise_type == 'gaussian':
-            return H_adj(H(x) - y) / (self.args.sigma_noise ** 2)
-        elif self.args.noise_type == 'laplace':
-            r = H(x) - y
-            return H_adj(2 * torch.heaviside(r, torch.zeros_like(r)) - 1) / self.args.sigma_noise
-        raise ValueError('Noise type not supported')
 
     def prox_datafit(self, x, y, H, H_adj, degradation=None, alpha=None):
         """pnp_gs.py:32-44 (the unreachable superresolution_bicubic branch is not implemented)."""
@@ -138,9 +114,9 @@ class PROX_PNP(object):
             raise _lib.PnpFlowHipError("PROX_PNP needs GPU tensors (there is no CPU path)")
         B, Hh = noisy_img.shape[0], self.model.input_height
         y = noisy_img.detach().contiguous().float()
-        x = (self.initialise(y, degradation) if x0 is None else x0.detach().clone()).to(y.device).contiguous().float()
-        if tuple(x.shape) != (B, self.model.input_channels, Hh, Hh):
-            raise ValueError(f"iterate of shape {tuple(x.shape)} does not match the net's (B, {self.model.input_channels}, {Hh}, {Hh})")
+        x = _harness.check_image((self.initialise(y, degradation) if x0 is None else x0.detach().clone()).to(y.device), "iterate", self.model, "PROX_PNP")
+        if x.shape[0] != B:
+            raise ValueError(f"iterate of shape {tuple(x.shape)} does not match the measurement's batch of {B}")
         d = degradation.descriptor(B, Hh, Hh, y.device)
         lr = sigma_noise ** 2 * args.lr_pnp if lr is None else lr
         tab = self.level_table(sigma_noise)
@@ -152,43 +128,23 @@ class PROX_PNP(object):
         prm.grad_coef = float(lr) / (sigma_noise ** 2 if args.noise_type == "gaussian" else sigma_noise)
         prm.alpha = float(args.alpha if alpha is None else alpha)
         prm.use_graph = 1 if self.use_graph else 0
-        holder = {"err": None}
-        self.last_callback_seconds = 0.0
-        if iter_cb is not None:
-            def _cb(it, user):
-                t_cb = perf_counter()
-                try:
-                    if holder["err"] is None:
-                        iter_cb(it, x)
-                except BaseException as exc:      # must not unwind through the C frames: re-raised below
-                    holder["err"] = exc
-                self.last_callback_seconds += perf_counter() - t_cb
-            cb = _lib.ITER_CB(_cb)
-            if cb_iterations is not None:
-                mask = np.zeros(max_iter, dtype=np.uint8)
-                mask[[i for i in cb_iterations if 0 <= i < max_iter]] = 1
-                holder["mask"] = mask
-                prm.host_cb_mask = mask.ctypes.data
-        else:
-            cb = C.cast(None, _lib.ITER_CB)
+        call = IterCallback(iter_cb, max_iter, cb_iterations)
+        call.attach(prm); call.bind(x)
         alpha_out = C.c_double(prm.alpha)
         log = np.zeros((max_iter, 2), dtype=np.float64)
         with _lib.solver_stream():       # engine launches and metric callbacks on ONE stream (a real one: graph capture)
             _lib.check(self.lib.pf_pnp_gs_restore(self.model.handle, C.byref(d), C.byref(prm), y.data_ptr(), x.data_ptr(), C.byref(alpha_out),
-                                                  log.ctypes.data_as(C.POINTER(C.c_double)), B, _lib.current_stream_ptr(), cb, None),
+                                                  log.ctypes.data_as(C.POINTER(C.c_double)), B, _lib.current_stream_ptr(), call.cb, None),
                        self.model.handle, "pf_pnp_gs_restore")
-        if holder["err"] is not None:
-            raise holder["err"]
+        self.last_callback_seconds = call.seconds
+        call.reraise()
         self.last_alpha = float(alpha_out.value)
         self.last_gap_log = log if code == 2 else None
         return x
 
     def solve_ip(self, test_loader, degradation, sigma_noise):
-        world = max(parallel.rank_world()[1], int(os.environ.get("WORLD_SIZE", "1")))
-        if world > 1:
-            # the hqs deblurring rule compares norms over the whole batch tensor: a split batch would take other alpha decisions
-            raise RuntimeError("pnp_gs runs on one GPU only: its hqs deblurring branch decays alpha on norms over the whole batch, "
-                               f"so a batch split over {world} ranks would change the result. Run it without torchrun.")
+        # the hqs deblurring rule compares norms over the whole batch tensor: a split batch would take other alpha decisions
+        _harness.single_gpu_only(_harness.env_world(), "pnp_gs runs on one GPU only: its hqs deblurring branch decays alpha on norms over the whole batch")
         self.algo_code()                    # an unsupported (algo, problem) pair fails before anything is drawn
         H, H_adj = degradation.H, degradation.H_adj
         self.args.sigma_noise = sigma_noise
@@ -203,58 +159,22 @@ class PROX_PNP(object):
             noisy_img = H(clean_img.clone().to(self.device))
             G = noisy_img.shape[0]
             gshape = tuple(noisy_img.shape)
-            if self.measurement_noise is not None:
-                noise = self.measurement_noise(batch, noisy_img)
-            elif self.args.noise_type == 'laplace':
-                # pnp_gs.py:107-110: a Laplace sample of scale sigma_noise (unit scale here, scaled below), drawn on the CPU generator
-                noise = torch.distributions.laplace.Laplace(torch.zeros(gshape), torch.ones(gshape)).sample().to(self.device)
-            elif self.args.noise_type == 'gaussian':
-                noise = utils.draw_measurement_noise(batch, gshape, 0, G, self.device, self.measurement_noise_source)      # pnp_gs.py:105-106
-            else:
-                raise ValueError('Noise type not supported')
+            # pnp_gs.py:105-110: gaussian after torch.manual_seed(batch); the Laplace sample (unit scale here, scaled below) is not re-seeded
+            noise = _harness.measurement_noise(self, batch, noisy_img, gshape, 0, G, self.args.noise_type)
             noisy_img = noisy_img + noise.to(self.device) * sigma_noise
             clean_img = clean_img.to('cpu')
-            if self.args.compute_time:
-                torch.cuda.synchronize(); t0 = perf_counter()
-            if self.args.compute_memory:
-                torch.cuda.reset_peak_memory_stats(self.device)
 
             def on_iter(iteration, x):
-                utils.compute_psnr(clean_img, noisy_img, x.detach().clone(), self.args, H_adj, iter=iteration)
-                utils.compute_ssim(clean_img, noisy_img, x.detach().clone(), self.args, H_adj, iter=iteration)
-                utils.compute_lpips(clean_img, noisy_img, x.detach().clone(), self.args, H_adj, iter=iteration)
+                self.write_metrics(clean_img, noisy_img, x, H_adj, iteration)
 
             log_its = [it for it in range(max_iter) if it % 10 == 0] if self.args.save_results else []      # pnp_gs.py:224
-            x = self.restore_batch(noisy_img, degradation, sigma_noise, lr=lr, alpha=alpha,
-                                   iter_cb=on_iter if self.args.save_results else None, cb_iterations=log_its)
-            alpha = self.last_alpha
-            self.last_restored = x
-            if self.args.compute_memory:
-                utils.save_memory_use({"batch": batch, "max_allocated": torch.cuda.max_memory_allocated(self.device) + self.model.memory_bytes()},
-                                      self.args)
-            if self.args.compute_time:
-                torch.cuda.synchronize()
-                utils.save_time_use({"batch": batch, "time_per_batch": perf_counter() - t0 - self.last_callback_seconds}, self.args)
-            if self.args.save_results:
-                last = max_iter - 1         # the final metrics carry the last loop index as `iter` (pnp_gs.py:239-244)
-                utils.save_images(clean_img, noisy_img, x.detach().clone(), self.args, H_adj, iter='final')
-                utils.compute_psnr(clean_img, noisy_img, x.detach().clone(), self.args, H_adj, iter=last)
-                utils.compute_ssim(clean_img, noisy_img, x.detach().clone(), self.args, H_adj, iter=last)
-                utils.compute_lpips(clean_img, noisy_img, x.detach().clone(), self.args, H_adj, iter=last)
-        if self.args.save_results:
-            utils.compute_average_psnr(self.args)
-            utils.compute_average_ssim(self.args)
-            utils.compute_average_lpips(self.args)
-        if self.args.compute_memory:
-            utils.compute_average_memory(self.args)
-        if self.args.compute_time:
-            utils.compute_average_time(self.args)
+            with _harness.batch_stats(self, batch):
+                x = self.restore_batch(noisy_img, degradation, sigma_noise, lr=lr, alpha=alpha,
+                                       iter_cb=on_iter if self.args.save_results else None, cb_iterations=log_its)
+                alpha = self.last_alpha
+                self.last_restored = x
+            self.write_final(clean_img, noisy_img, x, H_adj, max_iter - 1)         # pnp_gs.py:239-244
+        self.write_averages()
 
     def should_save_image(self, iteration, steps):
         return iteration % (steps // 5) == 0
-
-    def run_method(self, data_loaders, degradation, sigma_noise):
-        folder = utils.get_save_path_ip(self.args.dict_cfg_method)
-        self.args.save_path_ip = os.path.join(self.args.save_path, folder)
-        os.makedirs(self.args.save_path_ip, exist_ok=True)
-        self.solve_ip(data_loaders[self.args.eval_split], degradation, sigma_noise)
