@@ -64,12 +64,17 @@ __device__ unsigned long long* g_sp_dbg = nullptr;
 #define SP_STAMP(k) do { } while (0)
 #endif
 
-template <int MT, int NT, bool RES, int TERMS = 3>
+// NSPLIT = 2 (round 7): a conv of 2 x 32 NT output channels as two problems of 32 NT channels over the same pixels, "N-halves".  The half is a constant
+// of the WORKGROUP: the two workgroups of a pair (consecutive XCD-contiguous ranks: one XCD) walk the same tile range at the same time, one per
+// half, so the second reader of an activation patch finds it in L2.  The half moves base pointers in the prologue (output / residual / bias / statistics,
+// the weight images of the chunk table); the pixel stride of the result is the compile-time 32 NT NSPLIT; the chunk loop is the same instruction stream.
+template <int MT, int NT, bool RES, int TERMS = 3, int NSPLIT = 1>
 __global__ __launch_bounds__(256, 1) void conv_sp_kernel(const PPParams p) {
     constexpr int TH = sp_rows(MT), NPIX = sp_npix(MT), A9 = sp_a9(MT), PATCH = sp_patch(MT);
-    constexpr int TAPB = sp_tap(NT, TERMS), XB = sp_x(NT, TERMS), COUT = 32 * NT, OB = COUT * 4;        // OB: bytes of an output pixel
+    constexpr int TAPB = sp_tap(NT, TERMS), XB = sp_x(NT, TERMS), COUT = 32 * NT, CTOT = COUT * NSPLIT, OB = CTOT * 4;        // COUT: channels of this workgroup; OB: bytes of an output pixel
     constexpr int NFRAG = (TERMS == 3 ? 2 : 1) * (MT + NT), NMMA = TERMS * MT * NT;      // fragment reads / MFMAs of a tap
     static_assert(TERMS == 3 || TERMS == 1, "split terms");
+    static_assert(NSPLIT == 1 || NSPLIT == 2, "N-halves");
     static_assert(sp_y(NT, TERMS) % 4096 == 0 && 9 * TAPB >= XB, "refill rounds of 4 KiB; slot X's over-fetch stays inside the chunk image");
     // hand-counted vmcnt: the patch requests issued behind a refill and in front of the barrier that publishes it
     constexpr int REQ1 = sp_stage_0(A9, 4), REQ2 = A9 - REQ1 + 3;      // taps 0-3; taps 5-7 + the three coefficient loads of tap 7 (scale, shift, operand scale)
@@ -115,8 +120,11 @@ __global__ __launch_bounds__(256, 1) void conv_sp_kernel(const PPParams p) {
     const unsigned e_lane = (unsigned)((4 * hi + ((lane >> 3) & 3)) * OB + em * 16);
 
     // ---- this workgroup's tiles: XCD-contiguous ranges, a rotated start ------------------------------------------------------------------
-    const int G = gridDim.x;
-    const int rg = (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);
+    // (NSPLIT = 2: G / 8 is even - launch_conv_sp - so ranks 2 k and 2 k + 1 sit in one XCD; pair k owns the k-th of G / 2 tile ranges)
+    const int G = (int)gridDim.x / NSPLIT;
+    const int rg0 = (blockIdx.x & 7) * ((int)gridDim.x >> 3) + (blockIdx.x >> 3);
+    const int rg = NSPLIT == 2 ? rg0 >> 1 : rg0, half = NSPLIT == 2 ? rg0 & 1 : 0;
+    const int hoff = NSPLIT == 2 ? half * COUT : 0;      // first channel of this workgroup's half (added where a base pointer is used: NSPLIT = 1 stays the instruction stream it was)
     const int T = p.B << (p.lx + p.ly);
     const int t_begin = (int)((long)rg * T / G), t_end = (int)((long)(rg + 1) * T / G);
     const int ntl = t_end - t_begin;
@@ -224,7 +232,7 @@ __global__ __launch_bounds__(256, 1) void conv_sp_kernel(const PPParams p) {
             a += __shfl_xor(a, 16); q += __shfl_xor(q, 16);
             a += __shfl_xor(a, 32); q += __shfl_xor(q, 32);
             if (lane < 8) {
-                double* dst = p.stats_out + ((size_t)run_b * COUT + (j >> 2) * 32 + em * 4 + (j & 3)) * 2;
+                double* dst = p.stats_out + ((size_t)run_b * CTOT + hoff + (j >> 2) * 32 + em * 4 + (j & 3)) * 2;
                 unsafeAtomicAdd(dst, a); unsafeAtomicAdd(dst + 1, q);
             }
             run1[j] = 0.f; run2[j] = 0.f;
@@ -247,7 +255,7 @@ __global__ __launch_bounds__(256, 1) void conv_sp_kernel(const PPParams p) {
     float addv[NT]; float oscale = 0.f;
     auto tile_inputs = [&](const PPTile& tl) __attribute__((always_inline)) {
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) addv[nt] = p.addvec[(size_t)tl.b * p.addvec_bs + nt * 32 + ch_of_col];      // (conv_sp_supported: never null - the NT loads are counted in chunk 0's vmcnt)
+        for (int nt = 0; nt < NT; ++nt) addv[nt] = p.addvec[(size_t)tl.b * p.addvec_bs + hoff + nt * 32 + ch_of_col];      // (conv_sp_supported: never null - the NT loads are counted in chunk 0's vmcnt)
         const float inv_last = scale_c[8 * tl.b + 4 + seg_id[3]];
         oscale = p.out_scale * (1.0f / 256.0f) * inv_last;
         asm volatile("" : "+v"(oscale));      // (consumed HERE: no scalar load may stay in flight into the chunk loop)
@@ -256,8 +264,8 @@ __global__ __launch_bounds__(256, 1) void conv_sp_kernel(const PPParams p) {
         if (tl.b != run_b || run_n >= 32) { flush_stats(); run_b = tl.b; }
         ++run_n;
         const size_t pix0 = ((size_t)tl.b * p.H + tl.oy0 + wq * 2 * MT) * p.W + tl.ox0;
-        char* obase = reinterpret_cast<char*>(p.out + pix0 * COUT);
-        const char* rbase = RES ? reinterpret_cast<const char*>(p.residual + pix0 * COUT) : nullptr;
+        char* obase = reinterpret_cast<char*>(p.out + pix0 * CTOT + hoff);
+        const char* rbase = RES ? reinterpret_cast<const char*>(p.residual + pix0 * CTOT + hoff) : nullptr;
         float4 rv[3][4];      // residual of accumulator tiles k, k + 1, k + 2: requested TWO tiles ahead (one tile ahead part of the round trip was exposed: -3 % on the 64-channel level's residual launches, probe r05)
         if constexpr (RES) {
 #pragma unroll
@@ -418,7 +426,7 @@ __global__ __launch_bounds__(256, 1) void conv_sp_kernel(const PPParams p) {
     unsigned long long* const stamp_buf = g_sp_dbg;
 #endif
     // (seg_c1 / seg_c2: first chunks of K-segments 1 and 2 - the accumulator changes units there)
-    gptr wimg_next = (gptr)(uintptr_t)p.ch[1].wimg;      // weight image of the chunk behind the current one
+    gptr wimg_next = (gptr)(uintptr_t)(half ? p.wimg_h1[1] : p.ch[1].wimg);      // weight image of the chunk behind the current one
     Desc dn;            // descriptor of the chunk whose coefficients are fetched next (three ahead of the one being multiplied)
     Src sr;             // source of the requests of the current chunk (the chunk two ahead), prepared during the previous chunk
     // ---- one chunk: MFMAs of chunk (it, c) from patch SI; staging of the next chunk into patch SI ^ 1 (taps 0-3, 5, 6); requests of the
@@ -510,7 +518,7 @@ __global__ __launch_bounds__(256, 1) void conv_sp_kernel(const PPParams p) {
     // chunk table -> LDS (uniform scalar loads of the kernel argument, once per workgroup)
     for (int c = 0; c < nch; ++c) {
         if (tid == 0) {
-            const unsigned long long sp_ = (unsigned long long)(uintptr_t)p.ch[c].src, wp_ = (unsigned long long)(uintptr_t)p.ch[c].wimg;
+            const unsigned long long sp_ = (unsigned long long)(uintptr_t)p.ch[c].src, wp_ = (unsigned long long)(uintptr_t)(half ? p.wimg_h1[c] : p.ch[c].wimg);      // (the half's own image)
             *reinterpret_cast<uint4*>(smem + TAB + (unsigned)c * 32u) = make_uint4((unsigned)sp_, (unsigned)(sp_ >> 32), (unsigned)wp_, (unsigned)(wp_ >> 32));
             *reinterpret_cast<uint4*>(smem + TAB + (unsigned)c * 32u + 16u) = make_uint4((unsigned)p.ch[c].cstride, (unsigned)p.ch[c].coff, (unsigned)p.ch[c].gn_c0, (unsigned)p.ch[c].seg);
         }
@@ -522,7 +530,7 @@ __global__ __launch_bounds__(256, 1) void conv_sp_kernel(const PPParams p) {
 #pragma unroll
         for (int i = 0; i < A9; ++i) issue_one(cf0, s0, i);
         {
-            const char* w0 = reinterpret_cast<const char*>(p.ch[0].wimg);
+            const char* w0 = reinterpret_cast<const char*>(half ? p.wimg_h1[0] : p.ch[0].wimg);
 #pragma unroll
             for (int j = 0; j < (TERMS == 3 ? 9 * TAPB : XB) / 4096; ++j) glds16_sp(dma_lane, w0 + j * 4096, (unsigned)(j * 4096) + (unsigned)(wq * 1024));      // TERMS = 3: X | Y are contiguous, as the chunk image is; TERMS = 1: slot X (taps 0..4 + the round-up)
             if constexpr (TERMS != 3) {
@@ -585,14 +593,16 @@ __global__ __launch_bounds__(256, 1) void conv_sp_kernel(const PPParams p) {
 static int ilog2_exact_sp(int v) { int l = 0; while ((1 << l) < v) ++l; return (1 << l) == v ? l : -1; }
 
 bool conv_sp_supported(const ConvParams& p, int stride, int up, int terms) {
-    static const int mode = getenv("PNPFLOW_HIP_SP") ? atoi(getenv("PNPFLOW_HIP_SP")) : 1;      // test-only A/B switch: 0 off, 1 on, 2 the 128-channel level only, 3 on in the default mode only
+    static const int mode = getenv("PNPFLOW_HIP_SP") ? atoi(getenv("PNPFLOW_HIP_SP")) : 1;      // test-only A/B switch: 0 off, 1 on, 2 the 128-channel level only, 3 on in the default mode only, 4 as 1 but the 256-channel level stays on conv_dma
     if (mode == 0 || (terms != 3 && !(terms == 1 && mode != 3)) || stride != 1 || up != 0 || p.gnb_x != nullptr) return false;
-    if (p.Cout != 128 && !(p.Cout == 64 && mode == 1)) return false;
+    // Cout 256 (round 7): two N-halves of 128 channels (NSPLIT = 2), built for the default mode (terms 3) only
+    const int nsplit = p.Cout == 256 ? 2 : 1;
+    if (p.Cout != 128 && !(p.Cout == 64 && (mode == 1 || mode == 4)) && !(p.Cout == 256 && mode == 1 && terms == 3)) return false;
     if (p.out_cstride != p.Cout || (p.residual != nullptr && p.res_cstride != p.Cout)) return false;
     // the hand-counted vmcnt in front of the first barrier of a tile's chunk 0 counts the NT bias loads of tile_inputs: a launch without a
     // bias vector would wait NT operations too loosely - such launches stay on conv_mfma16
     if (p.addvec == nullptr) return false;
-    const int TH = p.Cout == 128 ? sp_rows(2) : sp_rows(4);      // 16 x 16-pixel workgroup tiles at 128 channels, 32 x 16 at 64
+    const int TH = p.Cout == 64 ? sp_rows(4) : sp_rows(2);      // 16 x 16-pixel workgroup tiles at 128 (and 2 x 128) channels, 32 x 16 at 64
     if (p.H % TH || p.W % 16 || p.Hs != p.H || p.Ws != p.W) return false;
     // the staging packs the patch-pixel offset py * W + px (py <= TH + 1, px <= 17) into 16 bits (pk[], issue_one): ADVICE r5 - the bound
     // depends on the tile height, W <= 1024 at Cout 64 / W <= 2048 at Cout 128
@@ -600,7 +610,8 @@ bool conv_sp_supported(const ConvParams& p, int stride, int up, int terms) {
     if (ilog2_exact_sp(p.H / TH) < 0 || ilog2_exact_sp(p.W / 16) < 0) return false;
     // the persistent grid pays its prologue and pipeline fill over >= 4 tiles per workgroup
     const int grid = persistent_grid();
-    if (grid < 8 || (long)p.B * (p.H / TH) * (p.W / 16) < 4L * grid) return false;
+    // (NSPLIT = 2: an item is a (tile, N-half); the workgroups pair up inside an XCD, so a grid of an even number of workgroups per XCD)
+    if (grid < 8 || (long)nsplit * p.B * (p.H / TH) * (p.W / 16) < 4L * grid || (nsplit == 2 && grid % 16 != 0)) return false;
     int nch = 0;
     for (int i = 0; i < p.nseg; ++i) {
         const ConvSeg& s = p.seg[i];
@@ -612,24 +623,28 @@ bool conv_sp_supported(const ConvParams& p, int stride, int up, int terms) {
     return p.gn_C > 0 && p.coef != nullptr && p.scale != nullptr;      // (with_coef: every GroupNorm-ed split-fp16 launch carries operand scales)
 }
 
-template <int MT, int NT, int TERMS>
+template <int MT, int NT, int TERMS, int NSPLIT = 1>
 static hipError_t launch_sp_t(const PPParams& p0, hipStream_t s) {
     static unsigned long long attr_set[2] = {0ull, 0ull};
     const bool res = p0.residual != nullptr;
-    const void* kern = res ? reinterpret_cast<const void*>(conv_sp_kernel<MT, NT, true, TERMS>) : reinterpret_cast<const void*>(conv_sp_kernel<MT, NT, false, TERMS>);
+    const void* kern = res ? reinterpret_cast<const void*>(conv_sp_kernel<MT, NT, true, TERMS, NSPLIT>) : reinterpret_cast<const void*>(conv_sp_kernel<MT, NT, false, TERMS, NSPLIT>);
     { hipError_t e = set_max_dynamic_lds_once(kern, attr_set[res ? 1 : 0], 160 * 1024); if (e != hipSuccess) return e; }
     const int grid = persistent_grid();
-    if (grid <= 0) return hipErrorInvalidConfiguration;
+    if (grid <= 0 || (NSPLIT == 2 && grid % 16 != 0)) return hipErrorInvalidConfiguration;
     PPParams p = p0;
     p.lx = ilog2_exact_sp(p.W / 16); p.ly = ilog2_exact_sp(p.H / sp_rows(MT));
     p.rot = 5;
-    if (res) hipLaunchKernelGGL((conv_sp_kernel<MT, NT, true, TERMS>), dim3(grid), dim3(256), sp_lds(MT, NT, TERMS), s, p);
-    else hipLaunchKernelGGL((conv_sp_kernel<MT, NT, false, TERMS>), dim3(grid), dim3(256), sp_lds(MT, NT, TERMS), s, p);
+    if (res) hipLaunchKernelGGL((conv_sp_kernel<MT, NT, true, TERMS, NSPLIT>), dim3(grid), dim3(256), sp_lds(MT, NT, TERMS), s, p);
+    else hipLaunchKernelGGL((conv_sp_kernel<MT, NT, false, TERMS, NSPLIT>), dim3(grid), dim3(256), sp_lds(MT, NT, TERMS), s, p);
     return hipGetLastError();
 }
 
 hipError_t launch_conv_sp(const PPParams& p0, hipStream_t s, int terms) {
-    if (p0.n9 < 2 || (p0.n9 & 1) || p0.n1 != 0 || (terms != 3 && terms != 1)) return hipErrorInvalidValue;
+    if (p0.n9 < 2 || (p0.n9 & 1) || p0.n9 > PP_MAXCH || p0.n1 != 0 || (terms != 3 && terms != 1)) return hipErrorInvalidValue;
+    if (p0.cout == 256) {      // two N-halves of 128 channels: every chunk carries the second half's weight image
+        for (int c = 0; c < p0.n9; ++c) if (p0.wimg_h1[c] == nullptr) return hipErrorInvalidValue;
+        return terms == 3 ? launch_sp_t<2, 4, 3, 2>(p0, s) : hipErrorInvalidValue;
+    }
     if (p0.cout == 128) return terms == 3 ? launch_sp_t<2, 4, 3>(p0, s) : launch_sp_t<2, 4, 1>(p0, s);
     if (p0.cout == 64) return terms == 3 ? launch_sp_t<4, 2, 3>(p0, s) : launch_sp_t<4, 2, 1>(p0, s);
     return hipErrorInvalidValue;

@@ -49,7 +49,7 @@ struct Op {
     ConvParams cp; int stride = 1, up = 0;
     int dma = 0;                                    // OP_CONV: 1 = conv_dma.hip (its operands were written by the OP_PREP in front of it)
     int terms = 0;                                  // OP_CONV: conv_terms() of the plan's precision mode - the TERMS form that matches the weight images chosen at build time
-    int use_pp = 0; PPParams ppp{};                 // OP_CONV: 1 = conv_pp.hip (persistent two-team kernel of the 32-channel level), 2 = conv_sp.hip (64- / 128-channel levels)
+    int use_pp = 0; PPParams ppp{};                 // OP_CONV: 1 = conv_pp.hip (persistent two-team kernel of the 32-channel level), 2 = conv_sp.hip (64- / 128-channel levels; the 256-channel level as two N-halves)
     PrepParams pp{};
     EdgeConvParams ep;
     TembParams tp;
@@ -484,7 +484,8 @@ static int attach_pp(Builder& bd, const ConvParams& p, int stride, int up, PPPar
     // precision mode 2 (one MFMA per product): the hi-only TERMS = 1 forms of both persistent kernels (round 6)
     const int terms = conv_terms(e);
     if (terms == 0) return 0;
-    const bool sp = (p.Cout == 128 || p.Cout == 64) && conv_sp_supported(p, stride, up, terms);
+    const bool sp = (p.Cout == 256 || p.Cout == 128 || p.Cout == 64) && conv_sp_supported(p, stride, up, terms);
+    const int sp_nt = p.Cout == 256 ? 4 : p.Cout / 32;      // Cout 256: two N-halves of 128 channels, one image per chunk and half
     if (!sp && !(p.Cout == 32 && conv_pp_supported(p, stride, up, terms))) return 0;
     q = PPParams{};
     q.cout = p.Cout;
@@ -502,9 +503,14 @@ static int attach_pp(Builder& bd, const ConvParams& p, int stride, int up, PPPar
             const std::string& wn = it->second.name; const int lo = it->second.lo + cc * kc;
             const wpack::Oihw w = oihw(e, wn);
             if (w.O != p.Cout || (sp && w.kk != 9)) return 0;
+            const std::string sp_key = wn + (terms == 1 ? "#sph" : "#sp") + std::to_string(p.Cout) + "_" + std::to_string(lo);
             k.wimg = !sp ? weight_image(e, wn + "#pp" + std::to_string(lo), [&] { return wpack::chunk_pp(w, lo); })
-                         : weight_image(e, wn + (terms == 1 ? "#sph" : "#sp") + std::to_string(p.Cout) + "_" + std::to_string(lo), [&] { return wpack::chunk_sp(w, lo, p.Cout / 32, terms); });
+                         : weight_image(e, p.Cout == 256 ? sp_key + "_h0" : sp_key, [&] { return wpack::chunk_sp(w, lo, sp_nt, terms, 0); });
             if (!k.wimg) return 0;
+            if (sp && p.Cout == 256) {
+                q.wimg_h1[n - 1] = weight_image(e, sp_key + "_h1", [&] { return wpack::chunk_sp(w, lo, sp_nt, terms, 128); });
+                if (!q.wimg_h1[n - 1]) return 0;
+            }
             (sg.taps == 9 ? q.n9 : q.n1) += 1;
         }
     }

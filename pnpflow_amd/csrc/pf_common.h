@@ -194,7 +194,7 @@ size_t conv_dma_a16_bytes(int B, int C, int Hs, int Ws, int terms);
 // conv_pp.hip: persistent two-team kernel of the full-resolution 32-channel level.  A launch is a list of 32-channel K-chunks (9-tap chunks
 // with GroupNorm(+SiLU) staging first, then raw 1-tap chunks of a folded 1x1 shortcut), each with its own LDS weight image
 // (layouts in weight_pack.h: wpack::chunk_pp; wpack::chunk_sp for the 16-channel chunks of conv_sp.hip).
-constexpr int PP_MAXCH = 24;     // conv_pp: <= 4 chunks of 32 channels; conv_sp: <= 24 chunks of 16 channels (cat[256, 128] -> 128)
+constexpr int PP_MAXCH = 32;     // conv_pp: <= 4 chunks of 32 channels; conv_sp: <= 32 chunks of 16 channels (cat[256, 256] -> 256)
 struct PPChunk {
     const float* src;     // NHWC source tensor of the chunk's K-segment
     const void* wimg;     // weight image of this chunk in global memory: taps * 4 KiB (conv_sp: 36 / 72 KiB per 16-channel chunk of 64 / 128 output channels)
@@ -207,15 +207,16 @@ struct PPChunk {
 struct PPParams {
     PPChunk ch[PP_MAXCH]; // n9 nine-tap chunks, then n1 one-tap chunks (conv_pp is instantiated per (n9, n1, residual); conv_sp walks n9 at run time)
     int n9, n1;
-    int cout;                             // 32: conv_pp.hip; 64 / 128: conv_sp.hip
+    int cout;                             // 32: conv_pp.hip; 64 / 128 / 256: conv_sp.hip (256: two N-halves of 128 channels, out / residual / addvec / stats_out over all 256)
     int B, H, W, lx, ly;                  // tiles per row / column = 1 << lx / 1 << ly (8 x 16-pixel tiles)
     int rot;                              // workgroup g starts (g * rot) % (tiles of its range) tiles into its range (set by the launcher)
     float* out; const float* addvec; int addvec_bs; const float* residual; float res_scale; double* stats_out; float out_scale;
     const float* coef; int coef_stride; const float* scale;      // ConvParams::coef / ::scale of the launch
+    const void* wimg_h1[PP_MAXCH];        // conv_sp at cout 256 only: per chunk, the weight image of output channels 128-255 (ch[c].wimg: channels 0-127)
 };
 bool conv_pp_supported(const ConvParams& p, int stride, int up, int terms);
 hipError_t launch_conv_pp(const PPParams& p, hipStream_t s, int terms = 3);      // terms 1: precision mode 2 (hi-only operands)
-bool conv_sp_supported(const ConvParams& p, int stride, int up, int terms);      // conv_sp.hip: one wave per SIMD, software-pipelined (Cout = 64 / 128)
+bool conv_sp_supported(const ConvParams& p, int stride, int up, int terms);      // conv_sp.hip: one wave per SIMD, software-pipelined (Cout = 64 / 128, 256 as two halves)
 hipError_t launch_conv_sp(const PPParams& p, hipStream_t s, int terms = 3);      // terms 1: precision mode 2 (hi-only operands and weight images)
 
 hipError_t launch_conv(const ConvParams& p, int stride, int up, hipStream_t s);

@@ -72,8 +72,10 @@ inline std::vector<half_t> chunk_pp(const Oihw& w, int lo) {
 
 // LDS image of ONE 16-channel K-chunk [lo, lo + 16) for conv_sp.hip (O = 32 NT): halfs, P as in slice16
 //   img[(((((tap * P + part) * NT + ntile) * 2 + khalf) * 32 + n) * 8 + i] = split16(w(32 ntile + col_channel(n), lo + 8 khalf + i, tap)).part
-// - one tap slot = P NT KiB (8 KiB at 128 channels and terms 3).  Requires w.O == 32 NT and lo + 16 <= w.I (not checked).
-inline std::vector<half_t> chunk_sp(const Oihw& w, int lo, int NT, int terms) {
+// - one tap slot = P NT KiB (8 KiB at 128 channels and terms 3).  `row0`: first output row of the image - the N-halves of a 256-channel conv are the
+// images of rows [0, 128) and [128, 256), each what the 128-row slice alone would give (w(row0 + 32 ntile + col_channel(n), ...) in the formula).
+// Requires row0 + 32 NT <= w.O and lo + 16 <= w.I (not checked).
+inline std::vector<half_t> chunk_sp(const Oihw& w, int lo, int NT, int terms, int row0 = 0) {
     const int P = terms == 1 ? 1 : 2;
     std::vector<half_t> img((size_t)w.kk * P * NT * 512, (half_t)0.f);
     size_t at = 0;
@@ -82,7 +84,7 @@ inline std::vector<half_t> chunk_sp(const Oihw& w, int lo, int NT, int terms) {
             for (int nt = 0; nt < NT; ++nt)
                 for (int kh = 0; kh < 2; ++kh)
                     for (int n = 0; n < 32; ++n)
-                        for (int i = 0; i < 8; ++i) img[at++] = split16(w(32 * nt + col_channel(n), lo + 8 * kh + i, tap)).part(part);
+                        for (int i = 0; i < 8; ++i) img[at++] = split16(w(row0 + 32 * nt + col_channel(n), lo + 8 * kh + i, tap)).part(part);
     return img;
 }
 
