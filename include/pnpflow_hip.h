@@ -140,18 +140,27 @@ typedef enum pf_degradation_kind {
     PF_DEG_GAUSSIAN_BLUR = 4,   /* GaussianDeblurring  degradations.py:55-89 (circular, separable) */
     PF_DEG_SR_FILTERED = 5,     /* Superresolution mode="bicubic": circular separable filter (utils.py:365-396), then decimation
                                    degradations.py:97-127; uses sf, ntaps (4*sf, even), taps */
-    PF_DEG_GAUSSIAN_BLUR_ZERO = 6 /* GaussianDeblurring, any mode but "fft" (degradations.py:72-76, 82-86): F.conv2d(padding='same'), i.e. the
+    PF_DEG_GAUSSIAN_BLUR_ZERO = 6,/* GaussianDeblurring, any mode but "fft" (degradations.py:72-76, 82-86): F.conv2d(padding='same'), i.e. the
                                    correlation with outer(taps, taps) where samples outside the image are 0; H_adj is the matching convolution
                                    (= H for the symmetric Gaussian).  Same fields as GAUSSIAN_BLUR (ntaps, taps); no ntaps < H restriction */
+    PF_DEG_PSF_BLUR = 7,        /* circular blur with any square 2-D point-spread function (what the reference computes when GaussianDeblurring's
+                                   `.filter` holds the PSF, degradations.py:62-89): H is the circular convolution y[i] = sum_j k[j] x[i - (j - r)],
+                                   r = K/2 on both axes, H_adj the circular correlation.  ntaps = K, the side of the K x K PSF: odd, 1 <= K <= 63,
+                                   K <= min(H, W) (the filter must hold the kernel); taps: device [K][K] row-major */
+    PF_DEG_PSF_BLUR_ZERO = 8    /* the same PSF where samples outside the image are 0: H is the correlation (F.conv2d(padding='same')), H_adj the
+                                   convolution - the true adjoint, which the reference's own spatial H_adj is not for an asymmetric kernel.
+                                   Same fields as PSF_BLUR; no size rule.  Both PSF kinds: an even K, K > 63 or NULL taps returns PF_ERR_INVALID */
 } pf_degradation_kind;
 
 typedef struct pf_degradation {
     int32_t kind;
     int32_t half_size_mask;     /* BOX */
     int32_t sf;                 /* SUPERRESOLUTION */
-    int32_t ntaps;              /* GAUSSIAN_BLUR / GAUSSIAN_BLUR_ZERO / SR_FILTERED: <= 127; tap ntaps/2 sits at offset 0 (the reference's roll by -(K-1)//2) */
+    int32_t ntaps;              /* GAUSSIAN_BLUR / GAUSSIAN_BLUR_ZERO / SR_FILTERED: <= 127; tap ntaps/2 sits at offset 0 (the reference's roll by -(K-1)//2).
+                                   PSF_BLUR / PSF_BLUR_ZERO: the side K of the square PSF; tap (K/2, K/2) sits at offset (0, 0) */
     const uint8_t* mask;        /* MASK: device [B][H][W] bytes, 1 = keep */
-    const float* taps;          /* GAUSSIAN_BLUR / GAUSSIAN_BLUR_ZERO / SR_FILTERED: device [ntaps] separable 1-D taps */
+    const float* taps;          /* GAUSSIAN_BLUR / GAUSSIAN_BLUR_ZERO / SR_FILTERED: device [ntaps] separable 1-D taps;
+                                   PSF_BLUR / PSF_BLUR_ZERO: device [ntaps][ntaps] row-major 2-D taps */
 } pf_degradation;
 
 /* y = H(x)      x:[B,C,H,W] -> y:[B,C,Hy,Wy]  (Hy = H/sf for SR, else H) */
@@ -164,7 +173,8 @@ int pf_degradation_H_adj(const pf_degradation* d, const float* y, float* x, int 
 /* ---- PnP-Flow iteration pieces (pnpflow/methods/pnp_flow.py) ------------------------- */
 /* z = x - coef[b] * H_adj(H(x) - y),  coef[b] = lr_t[b] / sigma^2
  * replaces grad_datafit + the update at pnp_flow.py:39-41, 109-112 (gaussian noise).
- * scratch: >= 2*B*C*H*W floats for GAUSSIAN_BLUR, GAUSSIAN_BLUR_ZERO and SR_FILTERED (pf_degradation_H/H_adj: B*C*H*W resp. 2*B*C*H*W), may be NULL otherwise. */
+ * scratch: >= 2*B*C*H*W floats for GAUSSIAN_BLUR, GAUSSIAN_BLUR_ZERO and SR_FILTERED (pf_degradation_H/H_adj: B*C*H*W resp. 2*B*C*H*W); >= B*C*H*W floats
+ * for PSF_BLUR and PSF_BLUR_ZERO (the residual between the two applications; their pf_degradation_H/H_adj need none and refuse x == y); may be NULL otherwise. */
 int pf_grad_step(const pf_degradation* d, const float* x, const float* y, const float* coef, float* z,
                  int B, int C, int H, int W, float* scratch, void* stream);
 /* Laplace noise model (pnp_flow.py:42-43): z = x - coef[b] * H_adj(2*heaviside(H(x) - y, 0) - 1), coef[b] = lr_t[b]/sigma */
@@ -247,11 +257,17 @@ int pf_unet_vjp(pf_engine* e, const float* x, const float* t, const float* vec, 
  *   x  += delta * (vt + coef[b] * (vec + one_minus_t[b]*g)),  coef = ((1-t)/t)*gamma
  * Closed form per pixel where H H^T is diagonal (denoising, masks, decimation: ot_ode.py:81-106); for
  * GAUSSIAN_BLUR the Fourier-domain solve of ot_ode.py:108-117 with a hand-written 2-D FFT, which needs
- * scratch >= 4*B*C*H*W + H + W floats (H, W <= 2048); scratch may be NULL for the other operators. */
+ * scratch >= 4*B*C*H*W + H + W floats (H, W <= 2048); PSF_BLUR takes the same solve with the 2-D table of pf_psf_power_spectrum and needs
+ * scratch >= 4*B*C*H*W + H*W floats; scratch may be NULL for the other operators.  GAUSSIAN_BLUR_ZERO and PSF_BLUR_ZERO have no closed form
+ * (pf_krylov_solve) and return PF_ERR_INVALID. */
 int pf_ot_ode_vec(const pf_degradation* d, const float* x, const float* vt, const float* y, const float* one_minus_t,
                   const float* rt2, float sigma2, float* vec, int B, int C, int H, int W, float* scratch, void* stream);
 int pf_ot_ode_update(float* x, const float* vt, const float* vec, const float* g, const float* one_minus_t,
                      const float* coef, float delta, int B, int n_per_image, void* stream);
+/* pw2[H][W] (device floats) <- |fft2(filter)|^2 of a PF_DEG_PSF_BLUR operator, the filter being the PSF zero-padded to H x W and rolled so that
+ * tap (K/2, K/2) sits at (0, 0) - the reference's `.filter` (degradations.py:62-68) - by a two-stage fp64 DFT of the K x K taps (along x, then
+ * along y).  What the Fourier solves divide by (ot_ode.py:108-118, pnp_gs.py:35-44); the engine's loops compute it once per call.  H, W <= 2048. */
+int pf_psf_power_spectrum(const pf_degradation* d, int H, int W, float* pw2, void* stream);
 
 /* Batched GMRES on the device (the reference's utils.GMRES, pnpflow/utils.py:972-1109, as ot_ode.py:119-128 calls it), all images at once:
  *   (rt2[b] H H^T + sigma2 I) sol[b] = rhs[b]
@@ -274,7 +290,7 @@ int pf_krylov_solve(const pf_degradation* d, const float* rt2_dev, float sigma2,
  * `delta * iteration**2` quirk for superresolution, ot_ode.py:96) read on the device through an iteration counter, the buffers
  * pre-allocated, and one hipGraph per Euler step (retained forward -> solve -> hand-written backward -> update) captured once
  * and replayed.  GAUSSIAN_BLUR_ZERO has no closed form: its step is the reference's generic branch (ot_ode.py:119-128) - retained forward,
- * d = y - H(x + (1-t) v_t), pf_krylov_solve (max_iter 100, tol = atol = 1e-6), vec = H_adj(sol), backward, update - as two captured halves with
+ * d = y - H(x + (1-t) v_t), pf_krylov_solve (max_iter 100, tol = atol = 1e-6; PSF_BLUR_ZERO takes the same path, PSF_BLUR the Fourier solve), vec = H_adj(sol), backward, update - as two captured halves with
  * the Krylov loop enqueued between them; pf_ot_ode_krylov_iterations reports how many Krylov iterations the last call enqueued.
  * x_inout: the initialisation t0*H_adj(y) + (1-t0)*noise on entry (ot_ode.py:27-28, 50-52), the result on exit. */
 typedef struct pf_ot_ode_params {

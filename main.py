@@ -40,8 +40,10 @@ def parse_args():
     return cfg
 
 
-def make_degradation(problem, dim_image, num_channels, noise_type, device):
-    """Problem table of the reference's main.py:120-179 -> (degradation, sigma_noise)."""
+def make_degradation(problem, dim_image, num_channels, noise_type, device, psf="motion", psf_size=None, psf_seed=0):
+    """Problem table of the reference's main.py:120-179 -> (degradation, sigma_noise), and the two point-spread-function problems
+    psf_deblurring_FFT (circular) / psf_deblurring (zero boundary): `psf` is "motion", "disk" or the path of a 2-D .npy file,
+    `psf_size` the side of a generated kernel (None: 31 at 128^2, 61 at 256^2), `psf_seed` the motion trajectory's seed."""
     from pnpflow_amd import degradations as D
     lap = noise_type == 'laplace'
     if problem == "denoising":
@@ -58,6 +60,11 @@ def make_degradation(problem, dim_image, num_channels, noise_type, device):
         return D.GaussianDeblurring({128: 1.0, 256: 3.0}[dim_image], 61, "fft", num_channels, dim_image, device), (0.3 if lap else 0.05)
     if problem == "gaussian_deblurring":      # the same blur with a zero boundary (degradations.py:72-76: any mode but "fft" is F.conv2d(padding='same'))
         return D.GaussianDeblurring({128: 1.0, 256: 3.0}[dim_image], 61, "spatial", num_channels, dim_image, device), (0.3 if lap else 0.05)
+    if problem in ("psf_deblurring_FFT", "psf_deblurring"):      # noise levels of the Gaussian blur
+        from pnpflow_amd import psf as P
+        size = int(psf_size) if psf_size is not None else {128: 31, 256: 61}[dim_image]
+        kernel = P.motion_psf(size, int(psf_seed)) if psf == "motion" else P.disk_psf(size, (size - 1) / 2.0) if psf == "disk" else P.load_psf(str(psf))
+        return D.PSFDeblurring(kernel, "fft" if problem == "psf_deblurring_FFT" else "spatial", num_channels, dim_image, device), (0.3 if lap else 0.05)
     raise ValueError("The problem you entered is not implemented by this engine: " + str(problem))
 
 
@@ -112,7 +119,8 @@ def main():
             raise FileNotFoundError(f"{model_path} not found (the reference's checkpoint, download.sh). "
                                     "Pass `--opts synthetic True` to run on seed-fixed synthetic weights instead.")
         model.eval()
-        degradation, sigma_noise = make_degradation(args.problem, args.dim_image, args.num_channels, args.noise_type, device)
+        degradation, sigma_noise = make_degradation(args.problem, args.dim_image, args.num_channels, args.noise_type, device, psf=getattr(args, "psf", "motion"),
+                                                    psf_size=getattr(args, "psf_size", None), psf_seed=getattr(args, "psf_seed", 0))
         if rank == 0:
             print('Solving the {} inverse problem with the method {}...'.format(args.problem, args.method))
             print('sigma_noise', sigma_noise)

@@ -212,6 +212,13 @@ struct DeviceGuard {
         }                                                                                      \
     } while (0)
 
+static const char* const PSF_TAPS_RULE = "the point-spread-function kinds need a device [K][K] taps array with K odd, 1 .. 63, and K <= the image side for the circular kind";
+
+static DegView to_view(const pf_degradation* d) {
+    DegView v{}; v.kind = d->kind; v.half = d->half_size_mask; v.sf = d->sf; v.ntaps = d->ntaps; v.mask = d->mask; v.taps = d->taps;
+    return v;
+}
+
 #include "solver_rt.inc"
 
 // --------------------------------------------------------------------------------------
@@ -1443,10 +1450,6 @@ __global__ void prep_iter_kernel(const int* iter, const float* t_all, const floa
 __global__ void bump_iter_kernel(int* iter) { if (threadIdx.x == 0) *iter += 1; }
 
 
-static DegView to_view(const pf_degradation* d) {
-    DegView v{}; v.kind = d->kind; v.half = d->half_size_mask; v.sf = d->sf; v.ntaps = d->ntaps; v.mask = d->mask; v.taps = d->taps;
-    return v;
-}
 
 // --------------------------------------------------------------------------------------
 // C ABI
@@ -1643,12 +1646,18 @@ int pf_unet_vjp(pf_engine* e, const float* x, const float* t, const float* vec, 
 int pf_ot_ode_vec(const pf_degradation* d, const float* x, const float* vt, const float* y, const float* one_minus_t, const float* rt2,
                   float sigma2, float* vec, int B, int C, int H, int W, float* scratch, void* stream) {
     if (!d || !x || !vt || !y || !one_minus_t || !rt2 || !vec) return PF_ERR_INVALID;
-    if (d->kind == PF_DEG_GAUSSIAN_BLUR) {
+    if (d->kind == PF_DEG_GAUSSIAN_BLUR || d->kind == PF_DEG_PSF_BLUR) {
         if (!scratch) return PF_ERR_INVALID;
         LAUNCHCHK(launch_ot_ode_vec_blur(to_view(d), x, vt, y, one_minus_t, rt2, sigma2, vec, B, C, H, W, scratch, (hipStream_t)stream));
         return PF_OK;
     }
     LAUNCHCHK(launch_ot_ode_vec(to_view(d), x, vt, y, one_minus_t, rt2, sigma2, vec, B, C, H, W, (hipStream_t)stream));
+    return PF_OK;
+}
+
+int pf_psf_power_spectrum(const pf_degradation* d, int H, int W, float* pw2, void* stream) {
+    if (!d || !pw2) return PF_ERR_INVALID;
+    LAUNCHCHK(launch_psf_power_spectrum(to_view(d), H, W, pw2, (hipStream_t)stream));
     return PF_OK;
 }
 
@@ -1856,6 +1865,7 @@ int pf_pnp_flow_restore(pf_engine* e, const pf_degradation* d, const pf_pnp_para
     const size_t n = (size_t)C * H * H;
     const int Hy = (d->kind == PF_DEG_SUPERRESOLUTION || d->kind == PF_DEG_SR_FILTERED) ? H / std::max(1, d->sf) : H;
     const size_t ny = (size_t)C * Hy * Hy;
+    if (deg_is_psf(d->kind) && !psf_taps_ok(to_view(d), H, H)) { e->err = std::string("pnp_flow: ") + PSF_TAPS_RULE; return PF_ERR_INVALID; }
     if ((rc = ensure_solver(e, B, n, ny, prm->steps, prm->batch_samples ? prm->num_samples : 1)) != PF_OK) return rc;
     SolverBufs& b = *e->sb;
     Plan* plan = nullptr;
@@ -1919,7 +1929,7 @@ constexpr int ODE_KRYLOV_MAX_ITER = 100;       // utils.GMRES(C_ope, d, max_iter
 
 // iterate, velocity, solve output, J^T vec, per-iteration schedule tables, cached graph(s)
 struct OdeBufs {
-    int B = 0; size_t n = 0, ny = 0; int steps = 0; int solve = 0 /* 0 closed form, 1 Fourier (circular blur), 2 Krylov (zero-boundary blur) */;
+    int B = 0; size_t n = 0, ny = 0; int steps = 0; int solve = 0 /* 0 closed form, 1 Fourier (circular Gaussian blur), 2 Krylov (zero-boundary blurs), 3 Fourier with the 2-D spectrum table (circular PSF) */;
     float *x = nullptr, *vt = nullptr, *vec = nullptr, *g = nullptr, *y = nullptr, *scratch = nullptr;
     float *dres = nullptr, *sol = nullptr, *kry = nullptr /* Krylov right-hand side, solution, workspace */; size_t kry_floats = 0;
     float *tab = nullptr /* [4][steps]: t, 1-t, r_t^2, coef */, *cur = nullptr /* [4][B] */; int* iter = nullptr;
@@ -1942,7 +1952,7 @@ static int ensure_ode(pf_engine* e, int B, size_t n, size_t ny, int steps, int s
     int rc = PF_OK;
     auto get = [&](auto** p, size_t bytes) { if (rc == PF_OK) rc = b.mem.alloc(e, p, bytes, 4); };
     get(&b.x, tot * 4); get(&b.vt, tot * 4); get(&b.vec, tot * 4); get(&b.g, tot * 4); get(&b.y, (size_t)B * ny * 4);
-    const size_t scr = solve == 1 ? 4 * tot + 2 * (size_t)H : solve == 2 ? tot : 0;
+    const size_t scr = solve == 1 ? 4 * tot + 2 * (size_t)H : solve == 3 ? 4 * tot + (size_t)H * H : solve == 2 ? tot : 0;
     if (scr) get(&b.scratch, scr * 4);
     if (solve == 2) {
         get(&b.dres, tot * 4); get(&b.sol, tot * 4);
@@ -1972,8 +1982,8 @@ static int enqueue_ode_step(pf_engine* e, Plan* plan, const DegView& dv, const p
     const float* t_cur = b.cur; const float* omt = b.cur + B; const float* rt2 = b.cur + 2 * B; const float* coef = b.cur + 3 * B;
     int rc = run_plan(e, plan, b.x, t_cur, b.vt, s, e->solver_time_scale);                                        // v_t = v_theta(x, t), activations retained
     if (rc != PF_OK) return rc;
-    hipError_t r = dv.kind == DEG_BLUR
-        ? launch_ot_ode_vec_blur(dv, b.x, b.vt, b.y, omt, rt2, prm->sigma2, b.vec, B, C, H, H, b.scratch, s)
+    hipError_t r = dv.kind == DEG_BLUR || dv.kind == DEG_PSF_BLUR       // (the PSF's spectrum table was filled once, before the loop)
+        ? launch_ot_ode_vec_blur(dv, b.x, b.vt, b.y, omt, rt2, prm->sigma2, b.vec, B, C, H, H, b.scratch, s, dv.kind == DEG_PSF_BLUR)
         : launch_ot_ode_vec(dv, b.x, b.vt, b.y, omt, rt2, prm->sigma2, b.vec, B, C, H, H, s);
     if (r != hipSuccess) { e->err = std::string("ot_ode vec: ") + hipGetErrorString(r); return PF_ERR_HIP; }
     if ((rc = run_backward(e, plan, b.vec, b.g, s)) != PF_OK) return rc;                     // g = J^T vec
@@ -2028,8 +2038,9 @@ int64_t pf_krylov_workspace_floats(int B, int C, int H, int W, int max_iter) {
 int pf_krylov_solve(const pf_degradation* d, const float* rt2_dev, float sigma2, const float* rhs, float* sol, int B, int C, int H, int W, int max_iter,
                     float tol, float atol, float* workspace, int64_t workspace_floats, int32_t* iters_out_dev, void* stream) {
     if (!d || !rt2_dev || !rhs || !sol || rhs == sol || !workspace || workspace_floats <= 0) return PF_ERR_INVALID;
-    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_GAUSSIAN_BLUR_ZERO || d->kind == PF_DEG_SUPERRESOLUTION || d->kind == PF_DEG_SR_FILTERED) return PF_ERR_INVALID;
+    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_PSF_BLUR_ZERO || d->kind == PF_DEG_SUPERRESOLUTION || d->kind == PF_DEG_SR_FILTERED) return PF_ERR_INVALID;
     if ((d->kind == PF_DEG_GAUSSIAN_BLUR || d->kind == PF_DEG_GAUSSIAN_BLUR_ZERO) && (!d->taps || d->ntaps < 1 || d->ntaps > 127)) return PF_ERR_INVALID;
+    if (deg_is_psf(d->kind) && !psf_taps_ok(to_view(d), H, W)) return PF_ERR_INVALID;
     if (d->kind == PF_DEG_MASK_INPAINTING && !d->mask) return PF_ERR_INVALID;
     LAUNCHCHK(launch_krylov_solve(to_view(d), rt2_dev, sigma2, rhs, sol, B, C, H, W, max_iter, tol, atol, workspace, (size_t)workspace_floats, iters_out_dev,
                                   (hipStream_t)stream));
@@ -2052,11 +2063,13 @@ int pf_ot_ode_restore(pf_engine* e, const pf_degradation* d, const pf_ot_ode_par
     const size_t n = (size_t)C * H * H;
     const int Hy = d->kind == PF_DEG_SUPERRESOLUTION ? H / std::max(1, d->sf) : H;
     const size_t ny = (size_t)C * Hy * Hy;
-    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_GAUSSIAN_BLUR_ZERO) { e->err = "ot_ode: unknown degradation kind"; return PF_ERR_INVALID; }
-    const bool krylov = d->kind == PF_DEG_GAUSSIAN_BLUR_ZERO;
-    if (krylov && (!d->taps || d->ntaps < 1 || d->ntaps > 127)) { e->err = "ot_ode: the zero-boundary blur needs 1 .. 127 device taps"; return PF_ERR_INVALID; }
+    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_PSF_BLUR_ZERO) { e->err = "ot_ode: unknown degradation kind"; return PF_ERR_INVALID; }
+    const bool krylov = d->kind == PF_DEG_GAUSSIAN_BLUR_ZERO || d->kind == PF_DEG_PSF_BLUR_ZERO;
+    if (d->kind == PF_DEG_GAUSSIAN_BLUR_ZERO && (!d->taps || d->ntaps < 1 || d->ntaps > 127)) { e->err = "ot_ode: the zero-boundary blur needs 1 .. 127 device taps"; return PF_ERR_INVALID; }
+    if (deg_is_psf(d->kind) && !psf_taps_ok(to_view(d), H, H)) { e->err = std::string("ot_ode: ") + PSF_TAPS_RULE; return PF_ERR_INVALID; }
+    if (d->kind == PF_DEG_PSF_BLUR && H > 2048) { e->err = "ot_ode: the Fourier solve needs H <= 2048"; return PF_ERR_INVALID; }
     e->ode_krylov_iters = 0;
-    if ((rc = ensure_ode(e, B, n, ny, prm->steps, krylov ? 2 : d->kind == PF_DEG_GAUSSIAN_BLUR ? 1 : 0, H)) != PF_OK) return rc;
+    if ((rc = ensure_ode(e, B, n, ny, prm->steps, krylov ? 2 : d->kind == PF_DEG_GAUSSIAN_BLUR ? 1 : d->kind == PF_DEG_PSF_BLUR ? 3 : 0, H)) != PF_OK) return rc;
     OdeBufs& b = *e->ob;
     Plan* plan = nullptr;
     if ((rc = build_plan(e, B, true, &plan)) != PF_OK) return rc;
@@ -2072,6 +2085,7 @@ int pf_ot_ode_restore(pf_engine* e, const pf_degradation* d, const pf_ot_ode_par
     HIPCHK(e, hipMemcpyAsync(b.iter, &first, sizeof(int), hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(b.y, y, (size_t)B * ny * 4, hipMemcpyDeviceToDevice, s));
     HIPCHK(e, hipMemcpyAsync(b.x, x_inout, (size_t)B * n * 4, hipMemcpyDeviceToDevice, s));
+    if (dv.kind == DEG_PSF_BLUR) HIPCHK(e, launch_psf_power_spectrum(dv, H, H, b.scratch + 4 * (size_t)B * n, s));      // once per call, not per step
     HIPCHK(e, hipStreamSynchronize(s));      // the host tables may go away after return
 
     OdeBufs::Key key; memset(&key, 0, sizeof key);

@@ -14,6 +14,7 @@ struct PnpGsState {
     float *y = nullptr, *hx = nullptr;                     // [B ny]
     float *scr = nullptr;                                  // [2 B n]: H / H_adj scratch, the FFT's complex plane
     float *pw = nullptr;                                   // [2 H]: separable factors of |fft2 filter|^2
+    float *pw2 = nullptr;                                  // [H H]: the spectrum of a point-spread function, allocated by the first hqs call with PF_DEG_PSF_BLUR
     float *tab = nullptr, *cur = nullptr, *coef = nullptr; // [max_iter] level table, [B] level of this iteration, [B] lr / sigma^2
     int* iter = nullptr;
     double* dbl = nullptr;                                 // [0] alpha, [1] |H(x) - y|^2 carried, [2] g, [8 ..) 3 x PNPGS_MAX_PARTS partials, then [max_iter][2] (gap, threshold)
@@ -83,7 +84,7 @@ static int enqueue_pnpgs_iteration(pf_engine* e, Plan* pr, const DegView& dv, co
     } else {
         if ((rc = enqueue_gs_grad(e, pr, st->x, st->cur, nullptr, s)) != PF_OK) return rc;
         GS_LAUNCH("combine", launch_pnpgs_combine(PNPGS_HQS_BLUR, st->x, st->N, st->JN, st->hadj, nullptr, alpha, st->rhs, B, (int64_t)st->n, (int64_t)H * H, s));
-        GS_LAUNCH("prox", launch_fft_prox_blur(st->rhs, alpha, st->pw, st->pw + H, st->z, B, C, H, H, st->scr, s));       // z: x_new
+        GS_LAUNCH("prox", launch_fft_prox_blur(st->rhs, alpha, st->pw, st->pw + H, st->z, B, C, H, H, st->scr, s, dv.kind == DEG_PSF_BLUR ? st->pw2 : nullptr));       // z: x_new
         GS_LAUNCH("H", launch_deg_H(dv, st->z, st->hx, B, C, H, H, st->scr, s));
         GS_LAUNCH("data term", launch_pnpgs_sqdist(st->hx, st->y, nullptr, st->part(0), toty, s));
         GS_LAUNCH("step length", launch_pnpgs_sqdist(st->z, st->x, st->x, st->part(1), tot, s));                                // and x <- x_new
@@ -132,7 +133,11 @@ int pf_pnp_gs_restore(pf_engine* e, const pf_degradation* d, const pf_pnp_gs_par
         e->err = "pnp_gs: algo 2 (hqs) has no zero-boundary form: its prox is a Fourier solve of the CIRCULAR blur (PF_DEG_GAUSSIAN_BLUR); use algo 0 (pgd) with PF_DEG_GAUSSIAN_BLUR_ZERO";
         return PF_ERR_INVALID;
     }
-    if (prm->algo == 2 && d->kind != PF_DEG_GAUSSIAN_BLUR) { e->err = "pnp_gs: algo 2 (hqs gaussian_deblurring_FFT) needs a PF_DEG_GAUSSIAN_BLUR operator"; return PF_ERR_INVALID; }
+    if (prm->algo == 2 && d->kind == PF_DEG_PSF_BLUR_ZERO) {
+        e->err = "pnp_gs: algo 2 (hqs) has no zero-boundary form: its prox is a Fourier solve of the CIRCULAR blur (PF_DEG_PSF_BLUR); use algo 0 (pgd) with PF_DEG_PSF_BLUR_ZERO";
+        return PF_ERR_INVALID;
+    }
+    if (prm->algo == 2 && d->kind != PF_DEG_GAUSSIAN_BLUR && d->kind != PF_DEG_PSF_BLUR) { e->err = "pnp_gs: algo 2 (hqs gaussian_deblurring_FFT) needs a PF_DEG_GAUSSIAN_BLUR operator"; return PF_ERR_INVALID; }
     if (prm->noise_model != 0 && prm->noise_model != 1) { e->err = "pnp_gs: noise_model must be 0 (gaussian) or 1 (laplace)"; return PF_ERR_INVALID; }
     if (prm->noise_model == 1 && prm->algo != 0) { e->err = "pnp_gs: the laplace noise model exists for algo 0 (pgd) only"; return PF_ERR_INVALID; }
     if (prm->max_iter <= 0 || prm->first < 0 || prm->first > prm->stop || prm->stop > prm->max_iter) {
@@ -140,7 +145,7 @@ int pf_pnp_gs_restore(pf_engine* e, const pf_degradation* d, const pf_pnp_gs_par
     }
     if (!prm->host_sigma_den) { e->err = "pnp_gs: host_sigma_den (the denoiser level of every iteration) is required"; return PF_ERR_INVALID; }
     if (!(prm->alpha > 0.0)) { e->err = "pnp_gs: alpha must be positive"; return PF_ERR_INVALID; }
-    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_GAUSSIAN_BLUR_ZERO) { e->err = "pnp_gs: unknown degradation kind"; return PF_ERR_INVALID; }
+    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_PSF_BLUR_ZERO) { e->err = "pnp_gs: unknown degradation kind"; return PF_ERR_INVALID; }
     const int C = e->cfg.input_channels, H = e->cfg.input_height;
     const bool sr = d->kind == PF_DEG_SUPERRESOLUTION || d->kind == PF_DEG_SR_FILTERED;
     if (sr && (d->sf <= 0 || H % d->sf)) { e->err = "pnp_gs: superresolution factor must divide the image size"; return PF_ERR_INVALID; }
@@ -150,6 +155,7 @@ int pf_pnp_gs_restore(pf_engine* e, const pf_degradation* d, const pf_pnp_gs_par
     if (d->kind == PF_DEG_GAUSSIAN_BLUR_ZERO && (!d->taps || d->ntaps < 1 || d->ntaps > 127)) {
         e->err = "pnp_gs: the zero-boundary blur needs 1..127 device taps"; return PF_ERR_INVALID;
     }
+    if (deg_is_psf(d->kind) && !psf_taps_ok(to_view(d), H, H)) { e->err = std::string("pnp_gs: ") + PSF_TAPS_RULE; return PF_ERR_INVALID; }
     if (d->kind == PF_DEG_MASK_INPAINTING && !d->mask) { e->err = "pnp_gs: mask inpainting needs a device mask"; return PF_ERR_INVALID; }
     const int Hy = sr ? H / d->sf : H;
     const size_t n = (size_t)C * H * H, ny = (size_t)C * Hy * Hy;
@@ -163,6 +169,7 @@ int pf_pnp_gs_restore(pf_engine* e, const pf_degradation* d, const pf_pnp_gs_par
     if (rc != PF_OK) return rc;
     if ((rc = ensure_pnpgs(e, B, n, ny, prm->max_iter)) != PF_OK) return rc;
     PnpGsState* st = e->pnpgs;
+    if (prm->algo == 2 && d->kind == PF_DEG_PSF_BLUR && !st->pw2 && (rc = st->mem.alloc4(e, &st->pw2, (size_t)H * H)) != PF_OK) return rc;
     Plan* pr = nullptr;
     if ((rc = build_plan(e, B, true, &pr)) != PF_OK) return rc;
     e->retained_B = B; e->retained_plan = pr;          // after the call: the retained forward of the last iteration's denoiser input
@@ -180,7 +187,8 @@ int pf_pnp_gs_restore(pf_engine* e, const pf_degradation* d, const pf_pnp_gs_par
         // once per call: H_adj(noisy), the filter's power spectrum and |H(x) - y|^2 of the entering iterate (afterwards carried by the decision kernel)
         HIPCHK(e, hipMemsetAsync(st->log(), 0, (size_t)2 * prm->max_iter * sizeof(double), s));
         GS_LAUNCH("H_adj", launch_deg_Hadj(dv, st->y, st->hadj, B, C, H, H, st->scr, s));
-        GS_LAUNCH("power spectrum", launch_blur_power_spectrum(dv, H, H, st->pw, st->pw + H, s));
+        if (dv.kind == DEG_PSF_BLUR) GS_LAUNCH("power spectrum", launch_psf_power_spectrum(dv, H, H, st->pw2, s));
+        else GS_LAUNCH("power spectrum", launch_blur_power_spectrum(dv, H, H, st->pw, st->pw + H, s));
         GS_LAUNCH("H", launch_deg_H(dv, st->x, st->hx, B, C, H, H, st->scr, s));
         GS_LAUNCH("data term", launch_pnpgs_sqdist(st->hx, st->y, nullptr, st->part(0), (int64_t)toty, s));
         GS_LAUNCH("data term", launch_pnpgs_sum(st->part(0), pnpgs_parts((int64_t)toty / 4), 1.0, st->dbl + 1, s));

@@ -90,7 +90,8 @@ __global__ __launch_bounds__(256) void fft_rows_fwd_kernel(const float* y, const
 // columns: forward FFT_H, divide by (rt2 * P_H[u] * P_W[v] + sigma2), inverse FFT_H - in place
 // alpha_dev != nullptr: the factor is the device scalar *alpha_dev for every image instead of rt2[image] (Prox-PnP's hqs deblurring prox,
 // pnp_gs.py:42: alpha |fft2 filter|^2 + 1 with sigma2 = 1)
-__global__ __launch_bounds__(256) void fft_cols_solve_kernel(float2* z, const float* pw_h, const float* pw_w, const float* rt2, const double* alpha_dev,
+// pw2 != nullptr: a point-spread function's spectrum does not factor; it is the table pw2[H][W] (psf_power_spectrum_kernel)
+__global__ __launch_bounds__(256) void fft_cols_solve_kernel(float2* z, const float* pw_h, const float* pw_w, const float* pw2, const float* rt2, const double* alpha_dev,
                                                              float sigma2, int C, int H, int W, int log2h, int LB) {
     extern __shared__ float2 smem[];
     float2* a = smem; float2* b = a + LB * H; float2* tw = b + LB * H;
@@ -107,8 +108,13 @@ __global__ __launch_bounds__(256) void fft_cols_solve_kernel(float2* z, const fl
     float2* o = r == a ? b : a;
     for (int idx = threadIdx.x; idx < LB * H; idx += 256) {
         const int l = idx / H, u = idx - l * H;
-        const float pv = col0 + l < W ? pw_w[col0 + l] : 0.f;
-        const float inv = r2 * (pw_h[u] * pv) + sigma2;           // ot_ode.py:113-115
+        float inv;
+        if (pw2) {
+            inv = r2 * (col0 + l < W ? pw2[(size_t)u * W + col0 + l] : 0.f) + sigma2;
+        } else {
+            const float pv = col0 + l < W ? pw_w[col0 + l] : 0.f;
+            inv = r2 * (pw_h[u] * pv) + sigma2;                   // ot_ode.py:113-115
+        }
         r[idx] = make_float2(r[idx].x / inv, r[idx].y / inv);     // :116
     }
     __syncthreads();
@@ -155,6 +161,44 @@ __global__ void blur_power_spectrum_kernel(const float* taps, int ntaps, int N, 
     pw[u] = (float)(re * re + im * im);
 }
 
+// P[u][v] = |DFT_HxW of the rolled, zero-padded K x K taps|^2 for a 2-D point-spread function, in fp64, as two stages: along x into one
+// complex value per tap row (the workgroup's column v of the K x W intermediate), then along y into the H values of column v.
+// One workgroup per column v; LDS: the H twiddles exp(-2 pi i m / H), then the K intermediate values.
+__global__ __launch_bounds__(256) void psf_power_spectrum_kernel(const float* taps, int K, int H, int W, float* pw2) {
+    extern __shared__ double2 s_spec[];
+    double2* tw = s_spec;
+    double2* T = tw + H;
+    const int v = blockIdx.x, r = K / 2;
+    for (int m = threadIdx.x; m < H; m += 256) {
+        double s, c;
+        sincospi(2.0 * (double)m / (double)H, &s, &c);
+        tw[m] = make_double2(c, -s);
+    }
+    for (int j = threadIdx.x; j < K; j += 256) {
+        double re = 0.0, im = 0.0;
+        for (int i = 0; i < K; ++i) {
+            long long m = ((long long)v * (i - r)) % W;            // exp(-2 pi i v (i-r) / W)
+            if (m < 0) m += W;
+            double s, c;
+            sincospi(2.0 * (double)m / (double)W, &s, &c);
+            re += (double)taps[j * K + i] * c; im -= (double)taps[j * K + i] * s;
+        }
+        T[j] = make_double2(re, im);
+    }
+    __syncthreads();
+    for (int u = threadIdx.x; u < H; u += 256) {
+        long long m0 = (-(long long)u * r) % H;                    // exp(-2 pi i u (j-r) / H), j = 0, then + u per tap row
+        int m = (int)(m0 < 0 ? m0 + H : m0);
+        double re = 0.0, im = 0.0;
+        for (int j = 0; j < K; ++j) {
+            const double2 w = tw[m], t = T[j];
+            re += t.x * w.x - t.y * w.y; im += t.x * w.y + t.y * w.x;
+            m += u; m -= m >= H ? H : 0;
+        }
+        pw2[(size_t)u * W + v] = (float)(re * re + im * im);
+    }
+}
+
 __global__ __launch_bounds__(256) void x1_hat_kernel(const float* x, const float* vt, const float* omt, float* out, int n, int64_t total) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256)
         out[i] = x[i] + omt[i / n] * vt[i];                       // ot_ode.py:74
@@ -166,15 +210,21 @@ inline int lines_per_wg(int N) { int lb = 2048 / N; return lb > 8 ? 8 : (lb < 1 
 }  // namespace
 
 // vec = H_adj( sol ),  sol = ifft2( fft2( y - H(x + (1-t) v_t) ) / (r_t^2 |fft2 filter|^2 + sigma^2) )
-// scratch: 4*B*C*H*W + H + W floats
+// scratch: 4*B*C*H*W + H + W floats; DEG_PSF_BLUR: 4*B*C*H*W + H*W (the 2-D spectrum table, filled here unless spectrum_ready)
 hipError_t launch_ot_ode_vec_blur(const DegView& d, const float* x, const float* vt, const float* y, const float* one_minus_t,
-                                  const float* rt2, float sigma2, float* vec, int B, int C, int H, int W, float* scratch, hipStream_t s) {
-    if (!scratch || d.kind != DEG_BLUR || H > 2048 || W > 2048 || d.ntaps > H || d.ntaps > W) return hipErrorInvalidValue;
+                                  const float* rt2, float sigma2, float* vec, int B, int C, int H, int W, float* scratch, hipStream_t s, bool spectrum_ready) {
+    const bool psf = d.kind == DEG_PSF_BLUR;
+    if (!scratch || (d.kind != DEG_BLUR && !psf) || H > 2048 || W > 2048 || d.ntaps > H || d.ntaps > W) return hipErrorInvalidValue;
     const size_t S = (size_t)B * C * H * W;
     float* buf0 = scratch; float* buf1 = scratch + S; float2* z = reinterpret_cast<float2*>(scratch + 2 * S);
     float* pw_h = scratch + 4 * S; float* pw_w = pw_h + H;
-    hipLaunchKernelGGL(blur_power_spectrum_kernel, dim3((H + 63) / 64), dim3(64), 0, s, d.taps, d.ntaps, H, pw_h);
-    hipLaunchKernelGGL(blur_power_spectrum_kernel, dim3((W + 63) / 64), dim3(64), 0, s, d.taps, d.ntaps, W, pw_w);
+    const float* pw2 = psf ? pw_h : nullptr;
+    if (psf) {
+        if (!spectrum_ready) { hipError_t e = launch_psf_power_spectrum(d, H, W, pw_h, s); if (e != hipSuccess) return e; }
+    } else {
+        hipLaunchKernelGGL(blur_power_spectrum_kernel, dim3((H + 63) / 64), dim3(64), 0, s, d.taps, d.ntaps, H, pw_h);
+        hipLaunchKernelGGL(blur_power_spectrum_kernel, dim3((W + 63) / 64), dim3(64), 0, s, d.taps, d.ntaps, W, pw_w);
+    }
     hipLaunchKernelGGL(x1_hat_kernel, dim3((unsigned)std::min<size_t>((S + 255) / 256, 4096)), dim3(256), 0, s, x, vt, one_minus_t, buf0,
                        C * H * W, (int64_t)S);
     hipError_t r = launch_deg_H(d, buf0, buf1, B, C, H, W, reinterpret_cast<float*>(z), s);          // buf1 = H(x1_hat)
@@ -182,12 +232,18 @@ hipError_t launch_ot_ode_vec_blur(const DegView& d, const float* x, const float*
     const int lbw = lines_per_wg(W), lbh = lines_per_wg(H);
     const size_t lds_w = (size_t)(2 * lbw + 1) * W * sizeof(float2), lds_h = (size_t)(2 * lbh + 1) * H * sizeof(float2);
     hipLaunchKernelGGL(fft_rows_fwd_kernel, dim3((H + lbw - 1) / lbw, B * C), dim3(256), lds_w, s, y, (const float*)buf1, z, H, W, ilog2_exact(W), lbw);
-    hipLaunchKernelGGL(fft_cols_solve_kernel, dim3((W + lbh - 1) / lbh, B * C), dim3(256), lds_h, s, z, (const float*)pw_h, (const float*)pw_w, rt2,
+    hipLaunchKernelGGL(fft_cols_solve_kernel, dim3((W + lbh - 1) / lbh, B * C), dim3(256), lds_h, s, z, (const float*)pw_h, (const float*)pw_w, pw2, rt2,
                        (const double*)nullptr, sigma2, C, H, W, ilog2_exact(H), lbh);
     hipLaunchKernelGGL(fft_rows_inv_kernel, dim3((H + lbw - 1) / lbw, B * C), dim3(256), lds_w, s, (const float2*)z, buf0, H, W, ilog2_exact(W), lbw);
     r = hipGetLastError();
     if (r != hipSuccess) return r;
     return launch_deg_Hadj(d, buf0, vec, B, C, H, W, buf1, s);                                        // vec = H_adj(sol), ot_ode.py:130
+}
+
+hipError_t launch_psf_power_spectrum(const DegView& d, int H, int W, float* pw2, hipStream_t s) {
+    if (d.kind != DEG_PSF_BLUR || !pw2 || H < 1 || W < 1 || H > 2048 || W > 2048 || !psf_taps_ok(d, H, W)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(psf_power_spectrum_kernel, dim3(W), dim3(256), (size_t)(H + d.ntaps) * sizeof(double2), s, d.taps, d.ntaps, H, W, pw2);
+    return hipGetLastError();
 }
 
 hipError_t launch_blur_power_spectrum(const DegView& d, int H, int W, float* pw_h, float* pw_w, hipStream_t s) {
@@ -201,13 +257,13 @@ hipError_t launch_blur_power_spectrum(const DegView& d, int H, int W, float* pw_
 //     out = real( ifft2( fft2(in) / (alpha |fft2 filter|^2 + 1) ) ),  in = alpha H_adj(y) + y'
 // the same three launches as the OT-ODE solve; alpha is read on the device.  cplx: 2*B*C*H*W floats
 hipError_t launch_fft_prox_blur(const float* in, const double* alpha_dev, const float* pw_h, const float* pw_w, float* out, int B, int C, int H, int W,
-                                float* cplx, hipStream_t s) {
-    if (!in || !alpha_dev || !pw_h || !pw_w || !out || !cplx || H > 2048 || W > 2048) return hipErrorInvalidValue;
+                                float* cplx, hipStream_t s, const float* pw2) {
+    if (!in || !alpha_dev || (!pw2 && (!pw_h || !pw_w)) || !out || !cplx || H > 2048 || W > 2048) return hipErrorInvalidValue;
     float2* z = reinterpret_cast<float2*>(cplx);
     const int lbw = lines_per_wg(W), lbh = lines_per_wg(H);
     const size_t lds_w = (size_t)(2 * lbw + 1) * W * sizeof(float2), lds_h = (size_t)(2 * lbh + 1) * H * sizeof(float2);
     hipLaunchKernelGGL(fft_rows_fwd_kernel, dim3((H + lbw - 1) / lbw, B * C), dim3(256), lds_w, s, in, (const float*)nullptr, z, H, W, ilog2_exact(W), lbw);
-    hipLaunchKernelGGL(fft_cols_solve_kernel, dim3((W + lbh - 1) / lbh, B * C), dim3(256), lds_h, s, z, pw_h, pw_w, (const float*)nullptr, alpha_dev, 1.0f,
+    hipLaunchKernelGGL(fft_cols_solve_kernel, dim3((W + lbh - 1) / lbh, B * C), dim3(256), lds_h, s, z, pw_h, pw_w, pw2, (const float*)nullptr, alpha_dev, 1.0f,
                        C, H, W, ilog2_exact(H), lbh);
     hipLaunchKernelGGL(fft_rows_inv_kernel, dim3((H + lbw - 1) / lbw, B * C), dim3(256), lds_w, s, (const float2*)z, out, H, W, ilog2_exact(W), lbw);
     return hipGetLastError();

@@ -240,7 +240,11 @@ hipError_t launch_softmax_bwd(const float* A, float* dA, int64_t rows, int cols,
 hipError_t launch_sumpool2(const float* in, float* out, int B, int H, int W, int C, int accumulate, hipStream_t s);
 
 // pointwise / operator kernels (NCHW fp32 images)
-enum { DEG_DENOISE = 0, DEG_BOX = 1, DEG_MASK = 2, DEG_SR = 3, DEG_BLUR = 4, DEG_SR_FILTER = 5, DEG_BLUR_ZERO = 6 /* same taps, samples outside the image are 0 */ };
+enum { DEG_DENOISE = 0, DEG_BOX = 1, DEG_MASK = 2, DEG_SR = 3, DEG_BLUR = 4, DEG_SR_FILTER = 5, DEG_BLUR_ZERO = 6 /* same taps, samples outside the image are 0 */,
+       DEG_PSF_BLUR = 7 /* circular blur with a square 2-D point-spread function: ntaps = its side K (odd, <= PSF_MAX_SIDE), taps = [K][K] */,
+       DEG_PSF_BLUR_ZERO = 8 /* the same taps, samples outside the image are 0 */ };
+constexpr int PSF_MAX_SIDE = 63;
+inline bool deg_is_psf(int kind) { return kind == DEG_PSF_BLUR || kind == DEG_PSF_BLUR_ZERO; }
 struct DegView {       // device-side view of pf_degradation
     int kind, half, sf, ntaps;
     const uint8_t* mask;
@@ -250,6 +254,13 @@ hipError_t launch_deg_H(const DegView& d, const float* x, float* y, int B, int C
 hipError_t launch_deg_Hadj(const DegView& d, const float* y, float* x, int B, int C, int H, int W, float* scratch, hipStream_t s);
 hipError_t launch_grad_step(const DegView& d, const float* x, const float* y, const float* coef, float* z,
                             int B, int C, int H, int W, float* scratch, int laplace, hipStream_t s);
+// the 2-D point-spread-function kinds (psf.hip): K odd, 1 .. PSF_MAX_SIDE, device taps, and K <= min(H, W) for the circular kind
+bool psf_taps_ok(const DegView& d, int H, int W);
+// one application in one launch, no scratch: sign +1 = H, -1 = H_adj; mode / aux / coef as blur2d_fused_kernel; in == out is refused
+hipError_t launch_psf2d(const DegView& d, const float* in, float* out, int B, int C, int H, int W, int sign, int mode, const float* aux, const float* coef,
+                        hipStream_t s);
+// pw2[H][W] <- |fft2(filter)|^2 of DEG_PSF_BLUR, the filter being the taps zero-padded to H x W with tap (K/2, K/2) at (0, 0) (fft2.hip)
+hipError_t launch_psf_power_spectrum(const DegView& d, int H, int W, float* pw2, hipStream_t s);
 hipError_t launch_interpolate(const float* z, const float* t, const float* noise, uint64_t seed, uint64_t stream_id,
                               float* zt, int B, int n, hipStream_t s);
 hipError_t launch_interp_iter(const float* z, const float* t, const float* noise, const unsigned long long* rng /* device [seed, stream_base, elem_offset] */,
@@ -273,8 +284,11 @@ hipError_t launch_scale_inplace(float* x, int64_t n, const float* scale, hipStre
 // OT-ODE per-pixel steps (pointwise.hip)
 hipError_t launch_ot_ode_vec(const DegView& d, const float* x, const float* vt, const float* y, const float* one_minus_t,
                              const float* rt2, float sigma2, float* vec, int B, int C, int H, int W, hipStream_t s);
+// scratch: 4*B*C*H*W + H + W floats (DEG_BLUR) or 4*B*C*H*W + H*W (DEG_PSF_BLUR: the 2-D spectrum table; spectrum_ready: the caller has
+// already filled it with launch_psf_power_spectrum(d, H, W, scratch + 4*B*C*H*W, s))
 hipError_t launch_ot_ode_vec_blur(const DegView& d, const float* x, const float* vt, const float* y, const float* one_minus_t,
-                                  const float* rt2, float sigma2, float* vec, int B, int C, int H, int W, float* scratch, hipStream_t s);
+                                  const float* rt2, float sigma2, float* vec, int B, int C, int H, int W, float* scratch, hipStream_t s,
+                                  bool spectrum_ready = false);
 hipError_t launch_ot_ode_update(float* x, const float* vt, const float* vec, const float* g, const float* one_minus_t, const float* coef,
                                 float delta, int B, int n, hipStream_t s);
 
@@ -333,8 +347,9 @@ hipError_t launch_pnpgs_decide(const double* p_new, int np_new, const double* p_
 // pw_h[H], pw_w[W] <- the separable factors of |fft2(blur filter)|^2
 hipError_t launch_blur_power_spectrum(const DegView& d, int H, int W, float* pw_h, float* pw_w, hipStream_t s);
 // out = real(ifft2(fft2(in) / (alpha |fft2 filter|^2 + 1))), alpha read from a device double; cplx: 2*B*C*H*W floats
+// pw2 != nullptr: the spectrum is the 2-D table pw2[H][W] (launch_psf_power_spectrum) and pw_h / pw_w are not read
 hipError_t launch_fft_prox_blur(const float* in, const double* alpha_dev, const float* pw_h, const float* pw_w, float* out, int B, int C, int H, int W,
-                                float* cplx, hipStream_t s);
+                                float* cplx, hipStream_t s, const float* pw2 = nullptr);
 
 // ---- Flow-Priors glue (flow_priors.hip); flat tensors of any length and alignment ------------------------------------------------
 struct AdamCoef;       // adam_step.h

@@ -396,6 +396,8 @@ hipError_t launch_deg_H(const DegView& d, const float* x, float* y, int B, int C
         case DEG_BLUR: case DEG_BLUR_ZERO:
             if (!scratch || !d.taps || d.ntaps < 1 || d.ntaps > 127) return hipErrorInvalidValue;
             return blur2(d, x, scratch, y, B, C, H, W, +1, 0, nullptr, nullptr, s);
+        case DEG_PSF_BLUR: case DEG_PSF_BLUR_ZERO:      // one launch, no scratch (psf.hip)
+            return launch_psf2d(d, x, y, B, C, H, W, +1, 0, nullptr, nullptr, s);
         case DEG_SR_FILTER: {      // y = decimate(filter (*) x)
             if (!scratch || d.ntaps < 1 || d.ntaps > 127 || d.sf <= 0 || H % d.sf || W % d.sf) return hipErrorInvalidValue;
             float* s0 = scratch; float* s1 = scratch + (size_t)B * C * H * W;
@@ -424,6 +426,8 @@ hipError_t launch_deg_Hadj(const DegView& d, const float* y, float* x, int B, in
         case DEG_BLUR: case DEG_BLUR_ZERO:
             if (!scratch || !d.taps || d.ntaps < 1 || d.ntaps > 127) return hipErrorInvalidValue;
             return blur2(d, y, scratch, x, B, C, H, W, -1, 0, nullptr, nullptr, s);
+        case DEG_PSF_BLUR: case DEG_PSF_BLUR_ZERO:
+            return launch_psf2d(d, y, x, B, C, H, W, -1, 0, nullptr, nullptr, s);
         case DEG_SR_FILTER: {      // x = filter^T (*) zerofill(y)
             if (!scratch || d.ntaps < 1 || d.ntaps > 127 || d.sf <= 0 || H % d.sf || W % d.sf) return hipErrorInvalidValue;
             float* s0 = scratch; float* s1 = scratch + (size_t)B * C * H * W;
@@ -511,6 +515,12 @@ hipError_t launch_grad_step(const DegView& d, const float* x, const float* y, co
             hipError_t e = blur2(d, x, s0, s1, B, C, H, W, +1, laplace ? 3 : 1, y, nullptr, s);     // s1 = Hx - y  (or its sign)
             if (e != hipSuccess) return e;
             return blur2(d, s1, s0, z, B, C, H, W, -1, 2, x, coef, s);                 // z = x - coef*H_adj(s1)
+        }
+        case DEG_PSF_BLUR: case DEG_PSF_BLUR_ZERO: {      // the same two applications; scratch: B*C*H*W floats (the residual)
+            if (!scratch || !psf_taps_ok(d, H, W)) return hipErrorInvalidValue;
+            hipError_t e = launch_psf2d(d, x, scratch, B, C, H, W, +1, laplace ? 3 : 1, y, nullptr, s);      // scratch = Hx - y  (or its sign)
+            if (e != hipSuccess) return e;
+            return launch_psf2d(d, scratch, z, B, C, H, W, -1, 2, x, coef, s);                              // z = x - coef*H_adj(scratch)
         }
         case DEG_SR_FILTER: {
             if (!scratch || d.ntaps < 1 || d.ntaps > 127 || d.sf <= 0 || H % d.sf || W % d.sf) return hipErrorInvalidValue;
@@ -762,6 +772,7 @@ hipError_t launch_ot_ode_vec(const DegView& d, const float* x, const float* vt, 
                              float sigma2, float* vec, int B, int C, int H, int W, hipStream_t s) {
     if (d.kind == DEG_BLUR) return hipErrorInvalidValue;   // Fourier-domain solve: launch_ot_ode_vec_blur (fft2.hip)
     if (d.kind == DEG_BLUR_ZERO) return hipErrorInvalidValue;   // no closed form: launch_krylov_solve (krylov.hip)
+    if (deg_is_psf(d.kind)) return hipErrorInvalidValue;        // DEG_PSF_BLUR: launch_ot_ode_vec_blur; DEG_PSF_BLUR_ZERO: launch_krylov_solve
     if (d.kind == DEG_SR && (d.sf <= 0 || H % d.sf || W % d.sf)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(ot_ode_vec_kernel, grid_for(C * H * W, B), dim3(256), 0, s, d, x, vt, y, one_minus_t, rt2, sigma2, vec, C, H, W);
     return hipGetLastError();

@@ -48,6 +48,7 @@ class Degradation:
             out = torch.empty((B, Cc, self.out_side(Hf), self.out_side(Wf)), dtype=torch.float32, device=x.device)
         if B == 0:
             return out          # an empty shard (global batch smaller than the number of ranks): nothing to launch
+        # (the point-spread-function kinds apply in one launch and need no scratch)
         n_scr = {_lib.PF_DEG_GAUSSIAN_BLUR: 1, _lib.PF_DEG_GAUSSIAN_BLUR_ZERO: 1, _lib.PF_DEG_SR_FILTERED: 2}.get(self.kind, 0)
         scratch = torch.empty((n_scr, B, Cc, Hf, Wf), dtype=torch.float32, device=x.device) if n_scr else None
         fn = lib.pf_degradation_H_adj if adjoint else lib.pf_degradation_H
@@ -306,3 +307,12 @@ class Superresolution(Degradation):
 
     def H_adj(self, x):
         return self._apply(x, True, out_hw=(x.shape[2] * self.sf, x.shape[3] * self.sf))
+
+
+def __getattr__(name):
+    """`degradations.PSFDeblurring` (the blur with any 2-D point-spread function) is defined in psf_deblurring.py, which imports this module's
+    Degradation, and is resolved on first use: this module's own namespace holds the reference's operator classes only."""
+    if name == "PSFDeblurring":
+        from .psf_deblurring import PSFDeblurring
+        return PSFDeblurring
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -58,8 +58,10 @@ class OT_ODE(Solver):
         self._set_time_scale()          # model_fn(x, t * 999), ot_ode.py:21-25
         # the zero-boundary blur has no closed-form solve either, but it is a table entry of main.py (problem gaussian_deblurring): the engine loop runs
         # the reference's generic branch for it with the batched GMRES on the device (pf_krylov_solve inside pf_ot_ode_restore)
-        krylov = getattr(degradation, "kind", None) == _lib.PF_DEG_GAUSSIAN_BLUR_ZERO
-        if not krylov and problem not in ("denoising", "inpainting", "random_inpainting", "paintbrush_inpainting", "superresolution", "gaussian_deblurring_FFT"):
+        # (the point-spread-function kinds are the Gaussian blurs' twins: PF_DEG_PSF_BLUR takes the Fourier solve, PF_DEG_PSF_BLUR_ZERO the Krylov one)
+        krylov = getattr(degradation, "kind", None) in (_lib.PF_DEG_GAUSSIAN_BLUR_ZERO, _lib.PF_DEG_PSF_BLUR_ZERO)
+        if not krylov and problem not in ("denoising", "inpainting", "random_inpainting", "paintbrush_inpainting", "superresolution", "gaussian_deblurring_FFT",
+                                          "psf_deblurring_FFT"):
             # OUT OF THE SURVEY 8 HOT-PATH SCOPE (unreachable for the five problems of main.py's table; kept from round 2,
             # host-orchestrated, golden-pinned, not part of any coverage claim): any other problem name takes the reference's generic
             # branch, a per-image GMRES on r_t^2 H H^T + sigma^2 I (ot_ode.py:118-128).

@@ -23,7 +23,9 @@ from .. import _lib
 from . import _harness
 from ._harness import IterCallback, Solver
 
-SUPPORTED = "algo pgd (any problem, gaussian or laplace noise), algo hqs with problem random_inpainting, algo hqs with problem gaussian_deblurring_FFT"
+SUPPORTED = ("algo pgd (any problem, gaussian or laplace noise), algo hqs with problem random_inpainting, algo hqs with problem gaussian_deblurring_FFT "
+             "or psf_deblurring_FFT")
+FFT_BLURS = ("gaussian_deblurring_FFT", "psf_deblurring_FFT")      # the circular blurs: hqs has a Fourier-domain prox for them
 
 
 class PROX_PNP(Solver):
@@ -44,7 +46,7 @@ class PROX_PNP(Solver):
         """pnp_gs.py:32-44 (the unreachable superresolution_bicubic branch is not implemented)."""
         if self.args.noise_type == 'gaussian' and self.args.problem == "random_inpainting":
             return H(y) - H(x) + x
-        if self.args.noise_type == 'gaussian' and self.args.problem == "gaussian_deblurring_FFT":
+        if self.args.noise_type == 'gaussian' and self.args.problem in FFT_BLURS:
             fft_d = torch.fft.fft2(alpha * H_adj(y) + x)
             fft_kernel = torch.fft.fft2(degradation.filter.to(x.device))
             inv = alpha * torch.conj(fft_kernel) * fft_kernel + 1.
@@ -60,18 +62,18 @@ class PROX_PNP(Solver):
 
     # ---- host schedule ---------------------------------------------------------------------------------------------------------
     def algo_code(self):
-        """0 pgd | 1 hqs random_inpainting | 2 hqs gaussian_deblurring_FFT.  The reference's loop matches no branch for any other
+        """0 pgd | 1 hqs random_inpainting | 2 hqs gaussian_deblurring_FFT / psf_deblurring_FFT.  The reference's loop matches no branch for any other
         pair and silently returns the initialisation; here that is an error."""
         algo, problem = self.args.algo, self.args.problem
         if algo == "pgd":
             return 0
         if algo == "hqs" and problem == "random_inpainting":
             return 1
-        if algo == "hqs" and problem == "gaussian_deblurring_FFT":
+        if algo == "hqs" and problem in FFT_BLURS:
             return 2
-        if algo == "hqs" and problem == "gaussian_deblurring":
-            raise ValueError("pnp_gs: algo 'hqs' has no form for problem 'gaussian_deblurring' (the zero-boundary blur): its prox is a Fourier solve of the "
-                             "circular operator (problem 'gaussian_deblurring_FFT'); use algo 'pgd'")
+        if algo == "hqs" and problem in ("gaussian_deblurring", "psf_deblurring"):
+            raise ValueError(f"pnp_gs: algo 'hqs' has no form for problem {problem!r} (the zero-boundary blur): its prox is a Fourier solve of the "
+                             f"circular operator (problem '{problem}_FFT'); use algo 'pgd'")
         raise ValueError(f"pnp_gs: algo {algo!r} with problem {problem!r} is not supported; supported: {SUPPORTED}")
 
     def level_table(self, sigma_noise):
