@@ -147,20 +147,25 @@ typedef enum pf_degradation_kind {
                                    `.filter` holds the PSF, degradations.py:62-89): H is the circular convolution y[i] = sum_j k[j] x[i - (j - r)],
                                    r = K/2 on both axes, H_adj the circular correlation.  ntaps = K, the side of the K x K PSF: odd, 1 <= K <= 63,
                                    K <= min(H, W) (the filter must hold the kernel); taps: device [K][K] row-major */
-    PF_DEG_PSF_BLUR_ZERO = 8    /* the same PSF where samples outside the image are 0: H is the correlation (F.conv2d(padding='same')), H_adj the
+    PF_DEG_PSF_BLUR_ZERO = 8,   /* the same PSF where samples outside the image are 0: H is the correlation (F.conv2d(padding='same')), H_adj the
                                    convolution - the true adjoint, which the reference's own spatial H_adj is not for an asymmetric kernel.
                                    Same fields as PSF_BLUR; no size rule.  Both PSF kinds: an even K, K > 63 or NULL taps returns PF_ERR_INVALID */
+    PF_DEG_PSF_SR = 9           /* superresolution through a blur kernel, y = (k (*) x) decimated by sf: H is the circular convolution of PSF_BLUR sampled at
+                                   (i sf, j sf), H_adj the zero-fill followed by the circular correlation - what the reference's Superresolution(mode="bicubic")
+                                   computes when its `.filter` holds the PSF (degradations.py:113-127).  sf: 1 .. 8, dividing H and W; ntaps = K odd, 1 .. 63,
+                                   K <= min(H, W); taps: device [K][K].  Anything else (also x == y) returns PF_ERR_INVALID on every entry point, before a launch.
+                                   H H^T is circulant on the low-resolution grid (pf_sr_aliased_spectrum), which gives OT-ODE and the hqs prox one Fourier solve */
 } pf_degradation_kind;
 
 typedef struct pf_degradation {
     int32_t kind;
     int32_t half_size_mask;     /* BOX */
-    int32_t sf;                 /* SUPERRESOLUTION */
+    int32_t sf;                 /* SUPERRESOLUTION, SR_FILTERED, PSF_SR */
     int32_t ntaps;              /* GAUSSIAN_BLUR / GAUSSIAN_BLUR_ZERO / SR_FILTERED: <= 127; tap ntaps/2 sits at offset 0 (the reference's roll by -(K-1)//2).
-                                   PSF_BLUR / PSF_BLUR_ZERO: the side K of the square PSF; tap (K/2, K/2) sits at offset (0, 0) */
+                                   PSF_BLUR / PSF_BLUR_ZERO / PSF_SR: the side K of the square PSF; tap (K/2, K/2) sits at offset (0, 0) */
     const uint8_t* mask;        /* MASK: device [B][H][W] bytes, 1 = keep */
     const float* taps;          /* GAUSSIAN_BLUR / GAUSSIAN_BLUR_ZERO / SR_FILTERED: device [ntaps] separable 1-D taps;
-                                   PSF_BLUR / PSF_BLUR_ZERO: device [ntaps][ntaps] row-major 2-D taps */
+                                   PSF_BLUR / PSF_BLUR_ZERO / PSF_SR: device [ntaps][ntaps] row-major 2-D taps */
 } pf_degradation;
 
 /* y = H(x)      x:[B,C,H,W] -> y:[B,C,Hy,Wy]  (Hy = H/sf for SR, else H) */
@@ -174,7 +179,8 @@ int pf_degradation_H_adj(const pf_degradation* d, const float* y, float* x, int 
 /* z = x - coef[b] * H_adj(H(x) - y),  coef[b] = lr_t[b] / sigma^2
  * replaces grad_datafit + the update at pnp_flow.py:39-41, 109-112 (gaussian noise).
  * scratch: >= 2*B*C*H*W floats for GAUSSIAN_BLUR, GAUSSIAN_BLUR_ZERO and SR_FILTERED (pf_degradation_H/H_adj: B*C*H*W resp. 2*B*C*H*W); >= B*C*H*W floats
- * for PSF_BLUR and PSF_BLUR_ZERO (the residual between the two applications; their pf_degradation_H/H_adj need none and refuse x == y); may be NULL otherwise. */
+ * for PSF_BLUR and PSF_BLUR_ZERO (the residual between the two applications; their pf_degradation_H/H_adj need none and refuse x == y); >= B*C*H*W / sf^2
+ * floats for PSF_SR (the low-resolution residual; H / H_adj need none); may be NULL otherwise. */
 int pf_grad_step(const pf_degradation* d, const float* x, const float* y, const float* coef, float* z,
                  int B, int C, int H, int W, float* scratch, void* stream);
 /* Laplace noise model (pnp_flow.py:42-43): z = x - coef[b] * H_adj(2*heaviside(H(x) - y, 0) - 1), coef[b] = lr_t[b]/sigma */
@@ -259,7 +265,10 @@ int pf_unet_vjp(pf_engine* e, const float* x, const float* t, const float* vec, 
  * GAUSSIAN_BLUR the Fourier-domain solve of ot_ode.py:108-117 with a hand-written 2-D FFT, which needs
  * scratch >= 4*B*C*H*W + H + W floats (H, W <= 2048); PSF_BLUR takes the same solve with the 2-D table of pf_psf_power_spectrum and needs
  * scratch >= 4*B*C*H*W + H*W floats; scratch may be NULL for the other operators.  GAUSSIAN_BLUR_ZERO and PSF_BLUR_ZERO have no closed form
- * (pf_krylov_solve) and return PF_ERR_INVALID. */
+ * (pf_krylov_solve) and return PF_ERR_INVALID.
+ * SR_FILTERED and PSF_SR (blur, then decimate): H H^T is circulant on the low-resolution grid, so the solve is the same three FFT launches on
+ * [H/sf][W/sf] with the aliased spectrum of pf_sr_aliased_spectrum:  vec = H_adj( ifft2_l( fft2_l(y - H(x1)) / (rt2 lam + sigma2) ) ).
+ * scratch >= pf_sr_solve_scratch_floats(B, C, H, W, sf) floats (4-byte alignment is enough: the complex plane is placed at an 8-byte boundary inside); H, W <= 2048. */
 int pf_ot_ode_vec(const pf_degradation* d, const float* x, const float* vt, const float* y, const float* one_minus_t,
                   const float* rt2, float sigma2, float* vec, int B, int C, int H, int W, float* scratch, void* stream);
 int pf_ot_ode_update(float* x, const float* vt, const float* vec, const float* g, const float* one_minus_t,
@@ -268,6 +277,17 @@ int pf_ot_ode_update(float* x, const float* vt, const float* vec, const float* g
  * tap (K/2, K/2) sits at (0, 0) - the reference's `.filter` (degradations.py:62-68) - by a two-stage fp64 DFT of the K x K taps (along x, then
  * along y).  What the Fourier solves divide by (ot_ode.py:108-118, pnp_gs.py:35-44); the engine's loops compute it once per call.  H, W <= 2048. */
 int pf_psf_power_spectrum(const pf_degradation* d, int H, int W, float* pw2, void* stream);
+/* lam[H/sf][W/sf] (device floats) <- the eigenvalues of the circulant H H^T of a PF_DEG_PSF_SR or PF_DEG_SR_FILTERED operator,
+ *   lam[u][v] = 1/sf^2 sum_{a, b < sf} |fft2(filter)|^2 [u + a H/sf][v + b W/sf],
+ * folded in fp64 from the 2-D table of pf_psf_power_spectrum (PSF_SR) or from the two separable factors (SR_FILTERED).
+ * tmp: device scratch of H*W floats (PSF_SR) or 2 (H + W) + 2 floats (SR_FILTERED: the folded factors are kept in fp64).  H, W <= 2048. */
+int pf_sr_aliased_spectrum(const pf_degradation* d, int H, int W, float* lam, float* tmp, void* stream);
+int64_t pf_sr_solve_scratch_floats(int B, int C, int H, int W, int sf);
+/* The exact proximal map of alpha/2 |H x - y|^2 for PSF_SR / SR_FILTERED by the Woodbury identity on the low-resolution grid:
+ *   out = in - alpha H_adj( ifft2_l( fft2_l(H in) / (alpha lam + 1) ) ),   in = z + alpha H_adj(y)  gives  out = prox(z).
+ * alpha_dev: device double; lam: pf_sr_aliased_spectrum; scratch >= pf_sr_solve_scratch_floats floats; in != out.  Two calls return the same bits. */
+int pf_sr_prox(const pf_degradation* d, const float* in, const double* alpha_dev, const float* lam, float* out, int B, int C, int H, int W, float* scratch,
+               void* stream);
 
 /* Batched GMRES on the device (the reference's utils.GMRES, pnpflow/utils.py:972-1109, as ot_ode.py:119-128 calls it), all images at once:
  *   (rt2[b] H H^T + sigma2 I) sol[b] = rhs[b]
@@ -429,6 +449,10 @@ int pf_gs_denoiser_grad(pf_engine* e, const float* x, const float* sigma, float*
  *                                                 x_new = real(ifft2(fft2(alpha H_adj(y) + y') / (alpha |fft2 filter|^2 + 1)));
  *                                                 alpha *= 0.9 when 0.5 |H(x_new) - y|^2 - 0.5 |H(x) - y|^2 < 0.1 / alpha |x_new - x|^2
  *                                                 (norms over the whole batch tensor)
+ *   algo 3 (hqs, superresolution through a blur kernel; the schedule of :180-200)  z = 0.065 alpha (x - Dg) + alpha (1 - 0.065 alpha) x;
+ *                                                 x_new = prox(z), the exact proximal map of alpha/2 |H x - y|^2 (pf_sr_prox with in = z + alpha H_adj(y));
+ *                                                 alpha never decays and there is no gap log.  The reference's own prox_datafit for this branch
+ *                                                 (pnp_gs.py:45-76) multiplies the aliased power spectrum by the data spectrum and is not a proximal map
  * The denoiser level of iteration i is host_sigma_den[i]; alpha lives in a device double (a decay needs no host round-trip).  One
  * iteration (retained forward, seed, hand-written backward, combine and, for algo 2, the Fourier prox, the reductions and the decision) is
  * captured once into a hipGraph and replayed while the plan, the operator, B, algo and the coefficients stay the same.  Reductions are
@@ -436,10 +460,10 @@ int pf_gs_denoiser_grad(pf_engine* e, const float* x, const float* sigma, float*
  * on entry, the iterate after iteration stop - 1 on exit.  host_alpha_out (host double[1], may be NULL): alpha after the call.
  * host_log (host double[2 * max_iter], may be NULL; algo 2): (gap, threshold) of every iteration run.  Afterwards the retained forward
  * is that of the last iteration's denoiser input.  Synchronises `stream` and checks the numeric health before returning.
- * PF_ERR_INVALID (no kernel launched): algo 1 without a PF_DEG_MASK_INPAINTING mask, algo 2 without PF_DEG_GAUSSIAN_BLUR, laplace with
- * algo != 0, first > stop or stop > max_iter. */
+ * PF_ERR_INVALID (no kernel launched): algo 1 without a PF_DEG_MASK_INPAINTING mask, algo 2 without PF_DEG_GAUSSIAN_BLUR, algo 3 without
+ * PF_DEG_PSF_SR / PF_DEG_SR_FILTERED, laplace with algo != 0, first > stop or stop > max_iter. */
 typedef struct pf_pnp_gs_params {
-    int32_t algo;                 /* 0 pgd | 1 hqs random_inpainting | 2 hqs gaussian_deblurring_FFT */
+    int32_t algo;                 /* 0 pgd | 1 hqs random_inpainting | 2 hqs gaussian_deblurring_FFT | 3 hqs superresolution_blur / superresolution_bicubic */
     int32_t noise_model;          /* 0 gaussian | 1 laplace (pgd only) */
     int32_t max_iter, first, stop;
     int32_t skip_grad_step;       /* pgd, gaussian denoising (pnp_gs.py:204-210) */

@@ -40,10 +40,19 @@ def parse_args():
     return cfg
 
 
-def make_degradation(problem, dim_image, num_channels, noise_type, device, psf="motion", psf_size=None, psf_seed=0):
+def psf_option(psf, psf_size, psf_seed, dim_image):
+    """The kernel of the `psf` / `psf_size` / `psf_seed` options: "motion", "disk" or the path of a 2-D .npy file; size None: 31 at 128^2, 61 at 256^2."""
+    from pnpflow_amd import psf as P
+    size = int(psf_size) if psf_size is not None else {128: 31, 256: 61}[dim_image]
+    return P.motion_psf(size, int(psf_seed)) if psf == "motion" else P.disk_psf(size, (size - 1) / 2.0) if psf == "disk" else P.load_psf(str(psf))
+
+
+def make_degradation(problem, dim_image, num_channels, noise_type, device, psf="motion", psf_size=None, psf_seed=0, sf=None):
     """Problem table of the reference's main.py:120-179 -> (degradation, sigma_noise), and the two point-spread-function problems
     psf_deblurring_FFT (circular) / psf_deblurring (zero boundary): `psf` is "motion", "disk" or the path of a 2-D .npy file,
-    `psf_size` the side of a generated kernel (None: 31 at 128^2, 61 at 256^2), `psf_seed` the motion trajectory's seed."""
+    `psf_size` the side of a generated kernel (None: 31 at 128^2, 61 at 256^2), `psf_seed` the motion trajectory's seed.
+    superresolution_blur: y = (psf (*) x) decimated by `sf` (None: what superresolution uses for the image size), the same `psf` options;
+    superresolution_bicubic: the reference's Superresolution(sf, S, mode="bicubic").  Both at the noise levels of superresolution."""
     from pnpflow_amd import degradations as D
     lap = noise_type == 'laplace'
     if problem == "denoising":
@@ -61,10 +70,13 @@ def make_degradation(problem, dim_image, num_channels, noise_type, device, psf="
     if problem == "gaussian_deblurring":      # the same blur with a zero boundary (degradations.py:72-76: any mode but "fft" is F.conv2d(padding='same'))
         return D.GaussianDeblurring({128: 1.0, 256: 3.0}[dim_image], 61, "spatial", num_channels, dim_image, device), (0.3 if lap else 0.05)
     if problem in ("psf_deblurring_FFT", "psf_deblurring"):      # noise levels of the Gaussian blur
-        from pnpflow_amd import psf as P
-        size = int(psf_size) if psf_size is not None else {128: 31, 256: 61}[dim_image]
-        kernel = P.motion_psf(size, int(psf_seed)) if psf == "motion" else P.disk_psf(size, (size - 1) / 2.0) if psf == "disk" else P.load_psf(str(psf))
+        kernel = psf_option(psf, psf_size, psf_seed, dim_image)
         return D.PSFDeblurring(kernel, "fft" if problem == "psf_deblurring_FFT" else "spatial", num_channels, dim_image, device), (0.3 if lap else 0.05)
+    if problem == "superresolution_bicubic":
+        return D.Superresolution({128: 2, 256: 4}[dim_image], dim_image, mode="bicubic", device=device), (0.3 if lap else 0.05)
+    if problem == "superresolution_blur":
+        kernel = psf_option(psf, psf_size, psf_seed, dim_image)
+        return D.PSFSuperresolution(kernel, int(sf) if sf is not None else {128: 2, 256: 4}[dim_image], num_channels, dim_image, device), (0.3 if lap else 0.05)
     raise ValueError("The problem you entered is not implemented by this engine: " + str(problem))
 
 
@@ -120,7 +132,7 @@ def main():
                                     "Pass `--opts synthetic True` to run on seed-fixed synthetic weights instead.")
         model.eval()
         degradation, sigma_noise = make_degradation(args.problem, args.dim_image, args.num_channels, args.noise_type, device, psf=getattr(args, "psf", "motion"),
-                                                    psf_size=getattr(args, "psf_size", None), psf_seed=getattr(args, "psf_seed", 0))
+                                                    psf_size=getattr(args, "psf_size", None), psf_seed=getattr(args, "psf_seed", 0), sf=getattr(args, "sf", None))
         if rank == 0:
             print('Solving the {} inverse problem with the method {}...'.format(args.problem, args.method))
             print('sigma_noise', sigma_noise)

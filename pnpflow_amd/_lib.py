@@ -18,7 +18,9 @@ PF_DEG_DENOISING, PF_DEG_BOX_INPAINTING, PF_DEG_MASK_INPAINTING, PF_DEG_SUPERRES
 PF_DEG_GAUSSIAN_BLUR_ZERO = 6      # zero-boundary Gaussian blur (GaussianDeblurring, any mode but "fft")
 PF_DEG_PSF_BLUR = 7                # circular blur with a square 2-D point-spread function (PSFDeblurring, mode "fft")
 PF_DEG_PSF_BLUR_ZERO = 8           # the same with samples outside the image 0 (PSFDeblurring, any other mode)
+PF_DEG_PSF_SR = 9                  # superresolution through a blur kernel: the circular PSF blur sampled at (i sf, j sf) (PSFSuperresolution)
 PSF_MAX_SIDE = 63
+PSF_SR_MAX_SF = 8
 
 
 class PfUnetCfg(C.Structure):
@@ -103,6 +105,9 @@ SIGNATURES = {
     "pf_unet_vjp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pf_ot_ode_vec": (C.c_int, [C.POINTER(PfDegradation), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "pf_psf_power_spectrum": (C.c_int, [C.POINTER(PfDegradation), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "pf_sr_aliased_spectrum": (C.c_int, [C.POINTER(PfDegradation), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pf_sr_solve_scratch_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "pf_sr_prox": (C.c_int, [C.POINTER(PfDegradation), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "pf_ot_ode_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_void_p]),
     "pf_engine_num_taps": (C.c_int, [C.c_void_p]),
     "pf_engine_tap_name": (C.c_char_p, [C.c_void_p, C.c_int]),

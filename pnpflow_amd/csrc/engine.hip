@@ -212,7 +212,7 @@ struct DeviceGuard {
         }                                                                                      \
     } while (0)
 
-static const char* const PSF_TAPS_RULE = "the point-spread-function kinds need a device [K][K] taps array with K odd, 1 .. 63, and K <= the image side for the circular kind";
+static const char* const PSF_TAPS_RULE = "the point-spread-function kinds need a device [K][K] taps array with K odd, 1 .. 63, and K <= the image side for the circular kinds; PF_DEG_PSF_SR also needs sf in 1 .. 8 dividing the image side";
 
 static DegView to_view(const pf_degradation* d) {
     DegView v{}; v.kind = d->kind; v.half = d->half_size_mask; v.sf = d->sf; v.ntaps = d->ntaps; v.mask = d->mask; v.taps = d->taps;
@@ -1646,7 +1646,7 @@ int pf_unet_vjp(pf_engine* e, const float* x, const float* t, const float* vec, 
 int pf_ot_ode_vec(const pf_degradation* d, const float* x, const float* vt, const float* y, const float* one_minus_t, const float* rt2,
                   float sigma2, float* vec, int B, int C, int H, int W, float* scratch, void* stream) {
     if (!d || !x || !vt || !y || !one_minus_t || !rt2 || !vec) return PF_ERR_INVALID;
-    if (d->kind == PF_DEG_GAUSSIAN_BLUR || d->kind == PF_DEG_PSF_BLUR) {
+    if (d->kind == PF_DEG_GAUSSIAN_BLUR || d->kind == PF_DEG_PSF_BLUR || d->kind == PF_DEG_PSF_SR || d->kind == PF_DEG_SR_FILTERED) {
         if (!scratch) return PF_ERR_INVALID;
         LAUNCHCHK(launch_ot_ode_vec_blur(to_view(d), x, vt, y, one_minus_t, rt2, sigma2, vec, B, C, H, W, scratch, (hipStream_t)stream));
         return PF_OK;
@@ -1658,6 +1658,24 @@ int pf_ot_ode_vec(const pf_degradation* d, const float* x, const float* vt, cons
 int pf_psf_power_spectrum(const pf_degradation* d, int H, int W, float* pw2, void* stream) {
     if (!d || !pw2) return PF_ERR_INVALID;
     LAUNCHCHK(launch_psf_power_spectrum(to_view(d), H, W, pw2, (hipStream_t)stream));
+    return PF_OK;
+}
+
+int pf_sr_aliased_spectrum(const pf_degradation* d, int H, int W, float* lam, float* tmp, void* stream) {
+    if (!d || !lam || !tmp) return PF_ERR_INVALID;
+    LAUNCHCHK(launch_sr_aliased_spectrum(to_view(d), H, W, lam, tmp, (hipStream_t)stream));
+    return PF_OK;
+}
+
+int64_t pf_sr_solve_scratch_floats(int B, int C, int H, int W, int sf) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || sf <= 0) return 0;
+    return (int64_t)sr_solve_scratch_floats(B, C, H, W, sf);
+}
+
+int pf_sr_prox(const pf_degradation* d, const float* in, const double* alpha_dev, const float* lam, float* out, int B, int C, int H, int W, float* scratch,
+               void* stream) {
+    if (!d || !in || !alpha_dev || !lam || !out || !scratch || B <= 0 || C <= 0) return PF_ERR_INVALID;
+    LAUNCHCHK(launch_fft_prox_sr(to_view(d), in, alpha_dev, lam, out, B, C, H, W, scratch, (hipStream_t)stream));
     return PF_OK;
 }
 
@@ -1863,7 +1881,7 @@ int pf_pnp_flow_restore(pf_engine* e, const pf_degradation* d, const pf_pnp_para
     const int C = e->cfg.input_channels, H = e->cfg.input_height;
     if (e->cfg.output_channels != C) { e->err = "restoration needs output_channels == input_channels"; return PF_ERR_INVALID; }
     const size_t n = (size_t)C * H * H;
-    const int Hy = (d->kind == PF_DEG_SUPERRESOLUTION || d->kind == PF_DEG_SR_FILTERED) ? H / std::max(1, d->sf) : H;
+    const int Hy = deg_is_sr(d->kind) ? H / std::max(1, d->sf) : H;
     const size_t ny = (size_t)C * Hy * Hy;
     if (deg_is_psf(d->kind) && !psf_taps_ok(to_view(d), H, H)) { e->err = std::string("pnp_flow: ") + PSF_TAPS_RULE; return PF_ERR_INVALID; }
     if ((rc = ensure_solver(e, B, n, ny, prm->steps, prm->batch_samples ? prm->num_samples : 1)) != PF_OK) return rc;
@@ -1929,7 +1947,7 @@ constexpr int ODE_KRYLOV_MAX_ITER = 100;       // utils.GMRES(C_ope, d, max_iter
 
 // iterate, velocity, solve output, J^T vec, per-iteration schedule tables, cached graph(s)
 struct OdeBufs {
-    int B = 0; size_t n = 0, ny = 0; int steps = 0; int solve = 0 /* 0 closed form, 1 Fourier (circular Gaussian blur), 2 Krylov (zero-boundary blurs), 3 Fourier with the 2-D spectrum table (circular PSF) */;
+    int B = 0; size_t n = 0, ny = 0; int steps = 0; int solve = 0 /* 0 closed form, 1 Fourier (circular Gaussian blur), 2 Krylov (zero-boundary blurs), 3 Fourier with the 2-D spectrum table (circular PSF), 4 Fourier on the low-resolution grid (blur, then decimate: PF_DEG_SR_FILTERED, PF_DEG_PSF_SR) */;
     float *x = nullptr, *vt = nullptr, *vec = nullptr, *g = nullptr, *y = nullptr, *scratch = nullptr;
     float *dres = nullptr, *sol = nullptr, *kry = nullptr /* Krylov right-hand side, solution, workspace */; size_t kry_floats = 0;
     float *tab = nullptr /* [4][steps]: t, 1-t, r_t^2, coef */, *cur = nullptr /* [4][B] */; int* iter = nullptr;
@@ -1952,7 +1970,9 @@ static int ensure_ode(pf_engine* e, int B, size_t n, size_t ny, int steps, int s
     int rc = PF_OK;
     auto get = [&](auto** p, size_t bytes) { if (rc == PF_OK) rc = b.mem.alloc(e, p, bytes, 4); };
     get(&b.x, tot * 4); get(&b.vt, tot * 4); get(&b.vec, tot * 4); get(&b.g, tot * 4); get(&b.y, (size_t)B * ny * 4);
-    const size_t scr = solve == 1 ? 4 * tot + 2 * (size_t)H : solve == 3 ? 4 * tot + (size_t)H * H : solve == 2 ? tot : 0;
+    // (solve 4: sr_solve_scratch_floats written out for a square image, sf^2 = n / ny)
+    const size_t scr = solve == 1 ? 4 * tot + 2 * (size_t)H : solve == 3 ? 4 * tot + (size_t)H * H : solve == 2 ? tot
+                     : solve == 4 ? 3 * tot + 3 * (size_t)B * ny + 1 + ny / (n / ((size_t)H * H)) + std::max((size_t)H * H, 4 * (size_t)H + 2) + (size_t)B : 0;
     if (scr) get(&b.scratch, scr * 4);
     if (solve == 2) {
         get(&b.dres, tot * 4); get(&b.sol, tot * 4);
@@ -1982,8 +2002,9 @@ static int enqueue_ode_step(pf_engine* e, Plan* plan, const DegView& dv, const p
     const float* t_cur = b.cur; const float* omt = b.cur + B; const float* rt2 = b.cur + 2 * B; const float* coef = b.cur + 3 * B;
     int rc = run_plan(e, plan, b.x, t_cur, b.vt, s, e->solver_time_scale);                                        // v_t = v_theta(x, t), activations retained
     if (rc != PF_OK) return rc;
-    hipError_t r = dv.kind == DEG_BLUR || dv.kind == DEG_PSF_BLUR       // (the PSF's spectrum table was filled once, before the loop)
-        ? launch_ot_ode_vec_blur(dv, b.x, b.vt, b.y, omt, rt2, prm->sigma2, b.vec, B, C, H, H, b.scratch, s, dv.kind == DEG_PSF_BLUR)
+    const bool sr_solve = dv.kind == DEG_PSF_SR || dv.kind == DEG_SR_FILTER;
+    hipError_t r = dv.kind == DEG_BLUR || dv.kind == DEG_PSF_BLUR || sr_solve      // (the PSF's spectrum table / the aliased spectrum was filled once, before the loop)
+        ? launch_ot_ode_vec_blur(dv, b.x, b.vt, b.y, omt, rt2, prm->sigma2, b.vec, B, C, H, H, b.scratch, s, dv.kind == DEG_PSF_BLUR || sr_solve)
         : launch_ot_ode_vec(dv, b.x, b.vt, b.y, omt, rt2, prm->sigma2, b.vec, B, C, H, H, s);
     if (r != hipSuccess) { e->err = std::string("ot_ode vec: ") + hipGetErrorString(r); return PF_ERR_HIP; }
     if ((rc = run_backward(e, plan, b.vec, b.g, s)) != PF_OK) return rc;                     // g = J^T vec
@@ -2038,7 +2059,7 @@ int64_t pf_krylov_workspace_floats(int B, int C, int H, int W, int max_iter) {
 int pf_krylov_solve(const pf_degradation* d, const float* rt2_dev, float sigma2, const float* rhs, float* sol, int B, int C, int H, int W, int max_iter,
                     float tol, float atol, float* workspace, int64_t workspace_floats, int32_t* iters_out_dev, void* stream) {
     if (!d || !rt2_dev || !rhs || !sol || rhs == sol || !workspace || workspace_floats <= 0) return PF_ERR_INVALID;
-    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_PSF_BLUR_ZERO || d->kind == PF_DEG_SUPERRESOLUTION || d->kind == PF_DEG_SR_FILTERED) return PF_ERR_INVALID;
+    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_PSF_SR || deg_is_sr(d->kind)) return PF_ERR_INVALID;
     if ((d->kind == PF_DEG_GAUSSIAN_BLUR || d->kind == PF_DEG_GAUSSIAN_BLUR_ZERO) && (!d->taps || d->ntaps < 1 || d->ntaps > 127)) return PF_ERR_INVALID;
     if (deg_is_psf(d->kind) && !psf_taps_ok(to_view(d), H, W)) return PF_ERR_INVALID;
     if (d->kind == PF_DEG_MASK_INPAINTING && !d->mask) return PF_ERR_INVALID;
@@ -2059,17 +2080,21 @@ int pf_ot_ode_restore(pf_engine* e, const pf_degradation* d, const pf_ot_ode_par
     if (rc != PF_OK) return rc;
     const int C = e->cfg.input_channels, H = e->cfg.input_height;
     if (e->cfg.output_channels != C) { e->err = "restoration needs output_channels == input_channels"; return PF_ERR_INVALID; }
-    if (d->kind == PF_DEG_SR_FILTERED) { e->err = "ot_ode: no closed-form solve for the filtered superresolution operator"; return PF_ERR_INVALID; }
     const size_t n = (size_t)C * H * H;
-    const int Hy = d->kind == PF_DEG_SUPERRESOLUTION ? H / std::max(1, d->sf) : H;
+    const bool sr_solve = d->kind == PF_DEG_SR_FILTERED || d->kind == PF_DEG_PSF_SR;      // H H^T is circulant on the low-resolution grid: one Fourier solve there
+    if (deg_is_sr(d->kind) && (d->sf <= 0 || H % d->sf)) { e->err = "ot_ode: superresolution factor must divide the image size"; return PF_ERR_INVALID; }
+    if (d->kind == PF_DEG_SR_FILTERED && (!d->taps || d->ntaps < 1 || d->ntaps > 127 || d->ntaps > H)) {
+        e->err = "ot_ode: the filtered superresolution operator needs 1 .. 127 device taps, no more than the image side"; return PF_ERR_INVALID;
+    }
+    const int Hy = deg_is_sr(d->kind) ? H / std::max(1, d->sf) : H;
     const size_t ny = (size_t)C * Hy * Hy;
-    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_PSF_BLUR_ZERO) { e->err = "ot_ode: unknown degradation kind"; return PF_ERR_INVALID; }
+    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_PSF_SR) { e->err = "ot_ode: unknown degradation kind"; return PF_ERR_INVALID; }
     const bool krylov = d->kind == PF_DEG_GAUSSIAN_BLUR_ZERO || d->kind == PF_DEG_PSF_BLUR_ZERO;
     if (d->kind == PF_DEG_GAUSSIAN_BLUR_ZERO && (!d->taps || d->ntaps < 1 || d->ntaps > 127)) { e->err = "ot_ode: the zero-boundary blur needs 1 .. 127 device taps"; return PF_ERR_INVALID; }
     if (deg_is_psf(d->kind) && !psf_taps_ok(to_view(d), H, H)) { e->err = std::string("ot_ode: ") + PSF_TAPS_RULE; return PF_ERR_INVALID; }
-    if (d->kind == PF_DEG_PSF_BLUR && H > 2048) { e->err = "ot_ode: the Fourier solve needs H <= 2048"; return PF_ERR_INVALID; }
+    if ((d->kind == PF_DEG_PSF_BLUR || sr_solve) && H > 2048) { e->err = "ot_ode: the Fourier solve needs H <= 2048"; return PF_ERR_INVALID; }
     e->ode_krylov_iters = 0;
-    if ((rc = ensure_ode(e, B, n, ny, prm->steps, krylov ? 2 : d->kind == PF_DEG_GAUSSIAN_BLUR ? 1 : d->kind == PF_DEG_PSF_BLUR ? 3 : 0, H)) != PF_OK) return rc;
+    if ((rc = ensure_ode(e, B, n, ny, prm->steps, krylov ? 2 : d->kind == PF_DEG_GAUSSIAN_BLUR ? 1 : d->kind == PF_DEG_PSF_BLUR ? 3 : sr_solve ? 4 : 0, H)) != PF_OK) return rc;
     OdeBufs& b = *e->ob;
     Plan* plan = nullptr;
     if ((rc = build_plan(e, B, true, &plan)) != PF_OK) return rc;
@@ -2086,6 +2111,10 @@ int pf_ot_ode_restore(pf_engine* e, const pf_degradation* d, const pf_ot_ode_par
     HIPCHK(e, hipMemcpyAsync(b.y, y, (size_t)B * ny * 4, hipMemcpyDeviceToDevice, s));
     HIPCHK(e, hipMemcpyAsync(b.x, x_inout, (size_t)B * n * 4, hipMemcpyDeviceToDevice, s));
     if (dv.kind == DEG_PSF_BLUR) HIPCHK(e, launch_psf_power_spectrum(dv, H, H, b.scratch + 4 * (size_t)B * n, s));      // once per call, not per step
+    if (sr_solve) {      // the aliased spectrum, likewise (the layout of launch_ot_ode_vec_blur's scratch for these kinds)
+        float* lam = sr_solve_lam(b.scratch, B, C, H, H, dv.sf);
+        HIPCHK(e, launch_sr_aliased_spectrum(dv, H, H, lam, lam + (size_t)Hy * Hy, s));
+    }
     HIPCHK(e, hipStreamSynchronize(s));      // the host tables may go away after return
 
     OdeBufs::Key key; memset(&key, 0, sizeof key);

@@ -5,7 +5,7 @@
 //                       r = x - N, the hand-written backward J^T r, Dg = r - J^T r (and g = 0.5 sum r^2).
 // pf_pnp_gs_restore     iterations [first, stop) of PROX_PNP.solve_ip's loop (pnp_gs.py:132-222) for one batch.  One iteration = retained
 //                       forward, seed, backward, combine (+ for hqs deblurring: Fourier prox, the three squared distances and the alpha
-//                       decision), captured once into a hipGraph and replayed; the denoiser level of the iteration is read from a device
+//                       decision; for hqs superresolution through a blur kernel, algo 3: the exact prox on the low-resolution grid), captured once into a hipGraph and replayed; the denoiser level of the iteration is read from a device
 //                       table through the iteration counter, alpha from a device double.
 
 struct PnpGsState {
@@ -15,6 +15,7 @@ struct PnpGsState {
     float *scr = nullptr;                                  // [2 B n]: H / H_adj scratch, the FFT's complex plane
     float *pw = nullptr;                                   // [2 H]: separable factors of |fft2 filter|^2
     float *pw2 = nullptr;                                  // [H H]: the spectrum of a point-spread function, allocated by the first hqs call with PF_DEG_PSF_BLUR
+    float *srs = nullptr, *lam = nullptr;                  // algo 3, allocated by its first call: launch_fft_prox_sr's scratch [3 B n + 3 B ny + 1 + B], then the spectrum's source, the aliased spectrum [Hy Hy]
     float *tab = nullptr, *cur = nullptr, *coef = nullptr; // [max_iter] level table, [B] level of this iteration, [B] lr / sigma^2
     int* iter = nullptr;
     double* dbl = nullptr;                                 // [0] alpha, [1] |H(x) - y|^2 carried, [2] g, [8 ..) 3 x PNPGS_MAX_PARTS partials, then [max_iter][2] (gap, threshold)
@@ -81,6 +82,11 @@ static int enqueue_pnpgs_iteration(pf_engine* e, Plan* pr, const DegView& dv, co
     } else if (prm->algo == 1) {
         if ((rc = enqueue_gs_grad(e, pr, st->x, st->cur, nullptr, s)) != PF_OK) return rc;
         GS_LAUNCH("combine", launch_pnpgs_combine(PNPGS_HQS_MASK, st->x, st->N, st->JN, st->y, dv.mask, nullptr, st->x, B, (int64_t)st->n, (int64_t)H * H, s));
+    } else if (prm->algo == 3) {
+        // pnp_gs.py:180-200 with the exact prox: rhs = alpha H_adj(noisy) + 0.065 alpha Dx + alpha (1 - 0.065 alpha) x, x <- prox; alpha never decays, no gap log
+        if ((rc = enqueue_gs_grad(e, pr, st->x, st->cur, nullptr, s)) != PF_OK) return rc;
+        GS_LAUNCH("combine", launch_pnpgs_combine(PNPGS_HQS_SR, st->x, st->N, st->JN, st->hadj, nullptr, alpha, st->rhs, B, (int64_t)st->n, (int64_t)H * H, s));
+        GS_LAUNCH("prox", launch_fft_prox_sr(dv, st->rhs, alpha, st->lam, st->x, B, C, H, H, st->srs, s));
     } else {
         if ((rc = enqueue_gs_grad(e, pr, st->x, st->cur, nullptr, s)) != PF_OK) return rc;
         GS_LAUNCH("combine", launch_pnpgs_combine(PNPGS_HQS_BLUR, st->x, st->N, st->JN, st->hadj, nullptr, alpha, st->rhs, B, (int64_t)st->n, (int64_t)H * H, s));
@@ -127,7 +133,8 @@ int pf_pnp_gs_restore(pf_engine* e, const pf_degradation* d, const pf_pnp_gs_par
     if (!e || !d || !prm || !y || !x_inout || B <= 0) return PF_ERR_INVALID;
     if (!e->finalized) { e->err = "weights not finalized"; return PF_ERR_STATE; }
     if (e->cfg.output_channels != e->cfg.input_channels) { e->err = "pnp_gs needs output_channels == input_channels"; return PF_ERR_INVALID; }
-    if (prm->algo < 0 || prm->algo > 2) { e->err = "pnp_gs: algo must be 0 (pgd), 1 (hqs random_inpainting) or 2 (hqs gaussian_deblurring_FFT)"; return PF_ERR_INVALID; }
+    if (prm->algo < 0 || prm->algo > 3) { e->err = "pnp_gs: algo must be 0 (pgd), 1 (hqs random_inpainting), 2 (hqs gaussian_deblurring_FFT) or 3 (hqs superresolution through a blur kernel)"; return PF_ERR_INVALID; }
+    if (prm->algo == 3 && d->kind != PF_DEG_PSF_SR && d->kind != PF_DEG_SR_FILTERED) { e->err = "pnp_gs: algo 3 (hqs superresolution_blur / superresolution_bicubic) needs a PF_DEG_PSF_SR or PF_DEG_SR_FILTERED operator"; return PF_ERR_INVALID; }
     if (prm->algo == 1 && (d->kind != PF_DEG_MASK_INPAINTING || !d->mask)) { e->err = "pnp_gs: algo 1 (hqs random_inpainting) needs a PF_DEG_MASK_INPAINTING operator with a device mask"; return PF_ERR_INVALID; }
     if (prm->algo == 2 && d->kind == PF_DEG_GAUSSIAN_BLUR_ZERO) {
         e->err = "pnp_gs: algo 2 (hqs) has no zero-boundary form: its prox is a Fourier solve of the CIRCULAR blur (PF_DEG_GAUSSIAN_BLUR); use algo 0 (pgd) with PF_DEG_GAUSSIAN_BLUR_ZERO";
@@ -145,9 +152,9 @@ int pf_pnp_gs_restore(pf_engine* e, const pf_degradation* d, const pf_pnp_gs_par
     }
     if (!prm->host_sigma_den) { e->err = "pnp_gs: host_sigma_den (the denoiser level of every iteration) is required"; return PF_ERR_INVALID; }
     if (!(prm->alpha > 0.0)) { e->err = "pnp_gs: alpha must be positive"; return PF_ERR_INVALID; }
-    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_PSF_BLUR_ZERO) { e->err = "pnp_gs: unknown degradation kind"; return PF_ERR_INVALID; }
+    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_PSF_SR) { e->err = "pnp_gs: unknown degradation kind"; return PF_ERR_INVALID; }
     const int C = e->cfg.input_channels, H = e->cfg.input_height;
-    const bool sr = d->kind == PF_DEG_SUPERRESOLUTION || d->kind == PF_DEG_SR_FILTERED;
+    const bool sr = deg_is_sr(d->kind);
     if (sr && (d->sf <= 0 || H % d->sf)) { e->err = "pnp_gs: superresolution factor must divide the image size"; return PF_ERR_INVALID; }
     if ((d->kind == PF_DEG_GAUSSIAN_BLUR || d->kind == PF_DEG_SR_FILTERED) && (!d->taps || d->ntaps < 1 || d->ntaps > 127 || d->ntaps > H)) {
         e->err = "pnp_gs: the filtered operators need 1..127 device taps (at most the image size)"; return PF_ERR_INVALID;
@@ -161,7 +168,7 @@ int pf_pnp_gs_restore(pf_engine* e, const pf_degradation* d, const pf_pnp_gs_par
     const size_t n = (size_t)C * H * H, ny = (size_t)C * Hy * Hy;
     if (n % 4 || ny % 4) { e->err = "pnp_gs: C*H*W (and the measurement's C*Hy*Wy) must be multiples of 4"; return PF_ERR_INVALID; }
     if (prm->algo == 1 && (H * H) % 4) { e->err = "pnp_gs: algo 1 needs H*W to be a multiple of 4"; return PF_ERR_INVALID; }
-    if (prm->algo == 2 && H > 2048) { e->err = "pnp_gs: algo 2 needs H <= 2048"; return PF_ERR_INVALID; }
+    if ((prm->algo == 2 || prm->algo == 3) && H > 2048) { e->err = "pnp_gs: algo 2 and algo 3 need H <= 2048"; return PF_ERR_INVALID; }
     USE_DEVICE(e);
     hipStream_t s = (hipStream_t)stream;
     const bool can_graph = prm->use_graph && !e->profile;
@@ -170,6 +177,10 @@ int pf_pnp_gs_restore(pf_engine* e, const pf_degradation* d, const pf_pnp_gs_par
     if ((rc = ensure_pnpgs(e, B, n, ny, prm->max_iter)) != PF_OK) return rc;
     PnpGsState* st = e->pnpgs;
     if (prm->algo == 2 && d->kind == PF_DEG_PSF_BLUR && !st->pw2 && (rc = st->mem.alloc4(e, &st->pw2, (size_t)H * H)) != PF_OK) return rc;
+    if (prm->algo == 3 && !st->srs) {      // (ensure_pnpgs resets the state, and these with it, when B, n or ny change)
+        if ((rc = st->mem.alloc4(e, &st->srs, 3 * (size_t)B * n + 3 * (size_t)B * ny + 1 + (size_t)B + std::max((size_t)H * H, 4 * (size_t)H + 2))) != PF_OK) return rc;
+        if ((rc = st->mem.alloc4(e, &st->lam, (size_t)Hy * Hy)) != PF_OK) return rc;
+    }
     Plan* pr = nullptr;
     if ((rc = build_plan(e, B, true, &pr)) != PF_OK) return rc;
     e->retained_B = B; e->retained_plan = pr;          // after the call: the retained forward of the last iteration's denoiser input
@@ -192,6 +203,11 @@ int pf_pnp_gs_restore(pf_engine* e, const pf_degradation* d, const pf_pnp_gs_par
         GS_LAUNCH("H", launch_deg_H(dv, st->x, st->hx, B, C, H, H, st->scr, s));
         GS_LAUNCH("data term", launch_pnpgs_sqdist(st->hx, st->y, nullptr, st->part(0), (int64_t)toty, s));
         GS_LAUNCH("data term", launch_pnpgs_sum(st->part(0), pnpgs_parts((int64_t)toty / 4), 1.0, st->dbl + 1, s));
+    }
+    if (prm->algo == 3) {
+        // once per call: H_adj(noisy) and the aliased spectrum (its source table goes into the tail of the prox scratch)
+        GS_LAUNCH("H_adj", launch_deg_Hadj(dv, st->y, st->hadj, B, C, H, H, st->scr, s));
+        GS_LAUNCH("aliased spectrum", launch_sr_aliased_spectrum(dv, H, H, st->lam, st->srs + 3 * tot + 3 * toty + 1 + (size_t)B, s));
     }
     HIPCHK(e, hipStreamSynchronize(s));      // the host table may go away after return
 

@@ -242,9 +242,12 @@ hipError_t launch_sumpool2(const float* in, float* out, int B, int H, int W, int
 // pointwise / operator kernels (NCHW fp32 images)
 enum { DEG_DENOISE = 0, DEG_BOX = 1, DEG_MASK = 2, DEG_SR = 3, DEG_BLUR = 4, DEG_SR_FILTER = 5, DEG_BLUR_ZERO = 6 /* same taps, samples outside the image are 0 */,
        DEG_PSF_BLUR = 7 /* circular blur with a square 2-D point-spread function: ntaps = its side K (odd, <= PSF_MAX_SIDE), taps = [K][K] */,
-       DEG_PSF_BLUR_ZERO = 8 /* the same taps, samples outside the image are 0 */ };
+       DEG_PSF_BLUR_ZERO = 8 /* the same taps, samples outside the image are 0 */,
+       DEG_PSF_SR = 9 /* the circular blur of DEG_PSF_BLUR sampled at (i sf, j sf): y = (k (*) x) decimated by sf (1 .. PSF_SR_MAX_SF, dividing H and W) */ };
 constexpr int PSF_MAX_SIDE = 63;
-inline bool deg_is_psf(int kind) { return kind == DEG_PSF_BLUR || kind == DEG_PSF_BLUR_ZERO; }
+constexpr int PSF_SR_MAX_SF = 8;
+inline bool deg_is_psf(int kind) { return kind == DEG_PSF_BLUR || kind == DEG_PSF_BLUR_ZERO || kind == DEG_PSF_SR; }      // the kinds with [K][K] taps (psf_taps_ok)
+inline bool deg_is_sr(int kind) { return kind == DEG_SR || kind == DEG_SR_FILTER || kind == DEG_PSF_SR; }                   // the measurement is [H / sf][W / sf]
 struct DegView {       // device-side view of pf_degradation
     int kind, half, sf, ntaps;
     const uint8_t* mask;
@@ -254,8 +257,13 @@ hipError_t launch_deg_H(const DegView& d, const float* x, float* y, int B, int C
 hipError_t launch_deg_Hadj(const DegView& d, const float* y, float* x, int B, int C, int H, int W, float* scratch, hipStream_t s);
 hipError_t launch_grad_step(const DegView& d, const float* x, const float* y, const float* coef, float* z,
                             int B, int C, int H, int W, float* scratch, int laplace, hipStream_t s);
-// the 2-D point-spread-function kinds (psf.hip): K odd, 1 .. PSF_MAX_SIDE, device taps, and K <= min(H, W) for the circular kind
+// the 2-D point-spread-function kinds (psf.hip): K odd, 1 .. PSF_MAX_SIDE, device taps, and K <= min(H, W) for the circular kinds; DEG_PSF_SR also
+// needs sf in 1 .. PSF_SR_MAX_SF dividing H and W
 bool psf_taps_ok(const DegView& d, int H, int W);
+// DEG_PSF_SR, one application in one launch, no scratch: sign +1 = H ([H][W] -> [H / sf][W / sf]), -1 = H_adj (the polyphase form: no zero-filled tensor);
+// mode / aux / coef as launch_psf2d, on the output's grid; in == out is refused
+hipError_t launch_psf_sr(const DegView& d, const float* in, float* out, int B, int C, int H, int W, int sign, int mode, const float* aux, const float* coef,
+                         hipStream_t s);
 // one application in one launch, no scratch: sign +1 = H, -1 = H_adj; mode / aux / coef as blur2d_fused_kernel; in == out is refused
 hipError_t launch_psf2d(const DegView& d, const float* in, float* out, int B, int C, int H, int W, int sign, int mode, const float* aux, const float* coef,
                         hipStream_t s);
@@ -289,6 +297,16 @@ hipError_t launch_ot_ode_vec(const DegView& d, const float* x, const float* vt, 
 hipError_t launch_ot_ode_vec_blur(const DegView& d, const float* x, const float* vt, const float* y, const float* one_minus_t,
                                   const float* rt2, float sigma2, float* vec, int B, int C, int H, int W, float* scratch, hipStream_t s,
                                   bool spectrum_ready = false);
+// DEG_PSF_SR / DEG_SR_FILTER (blur, then decimate by sf): launch_ot_ode_vec_blur takes them with scratch of sr_solve_scratch_floats(B, C, H, W, sf) floats;
+// spectrum_ready: the caller has filled lam = sr_solve_lam(scratch, ...) with launch_sr_aliased_spectrum(d, H, W, lam, lam + (H / sf) * (W / sf), s)
+size_t sr_solve_scratch_floats(int B, int C, int H, int W, int sf);
+float* sr_solve_lam(float* scratch, int B, int C, int H, int W, int sf);
+// lam[H / sf][W / sf] <- the eigenvalues of H H^T, 1 / sf^2 sum_{a, b < sf} |fft2 filter|^2 [u + a H / sf][v + b W / sf]; tmp: H*W floats (DEG_PSF_SR) or 2 (H + W) + 2 (DEG_SR_FILTER)
+hipError_t launch_sr_aliased_spectrum(const DegView& d, int H, int W, float* lam, float* tmp, hipStream_t s);
+// out = in - alpha H_adj( ifft2_l( fft2_l(H in) / (alpha lam + 1) ) ): with in = z + alpha H_adj(y) the exact prox of alpha/2 |H x - y|^2 at z.
+// alpha is read on the device; scratch: 3 S + 3 Sl + 1 + B floats; in != out
+hipError_t launch_fft_prox_sr(const DegView& d, const float* in, const double* alpha_dev, const float* lam, float* out, int B, int C, int H, int W, float* scratch,
+                              hipStream_t s);
 hipError_t launch_ot_ode_update(float* x, const float* vt, const float* vec, const float* g, const float* one_minus_t, const float* coef,
                                 float delta, int B, int n, hipStream_t s);
 
@@ -329,13 +347,13 @@ hipError_t launch_rk_aug(const RkAug& c, const double* logp, double* logp_new, d
 hipError_t launch_bpd_finish(const float* z, const double* delta_logp, double* partial, float* bpd, double offset, int B, int64_t n, hipStream_t s);
 
 // ---- Prox-PnP with the gradient-step denoiser: glue (prox_pnp.hip) and the Fourier prox (fft2.hip) ---------------------------
-enum { PNPGS_DG = 0, PNPGS_PGD = 1, PNPGS_HQS_MASK = 2, PNPGS_HQS_BLUR = 3 };      // output form of launch_pnpgs_combine
+enum { PNPGS_DG = 0, PNPGS_PGD = 1, PNPGS_HQS_MASK = 2, PNPGS_HQS_BLUR = 3, PNPGS_HQS_SR = 4 };      // output form of launch_pnpgs_combine
 constexpr int PNPGS_MAX_PARTS = 256;
 int pnpgs_parts(int64_t n4);         // fp64 partial sums per tensor for n4 float4 lanes (<= PNPGS_MAX_PARTS)
 // r = x - N; partial (or nullptr): pnpgs_parts(n / 4) partials of sum r^2
 hipError_t launch_pnpgs_seed(const float* x, const float* N, float* r, double* partial, int64_t n, hipStream_t s);
-// one pass over z, N, JN ([B][n]) -> out in the form `mode`; aux: the measurement (HQS_MASK) / H_adj(measurement) (HQS_BLUR);
-// mask: [B][hw] bytes (HQS_MASK; hw % 4 == 0); alpha_dev: device double (PGD, HQS_BLUR)
+// one pass over z, N, JN ([B][n]) -> out in the form `mode`; aux: the measurement (HQS_MASK) / H_adj(measurement) (HQS_BLUR, HQS_SR);
+// mask: [B][hw] bytes (HQS_MASK; hw % 4 == 0); alpha_dev: device double (PGD, HQS_BLUR, HQS_SR)
 hipError_t launch_pnpgs_combine(int mode, const float* z, const float* N, const float* JN, const float* aux, const uint8_t* mask, const double* alpha_dev,
                                 float* out, int B, int64_t n, int64_t hw, hipStream_t s);
 // pnpgs_parts(n / 4) partials of sum (a - b)^2; copy_to (or nullptr) <- a

@@ -398,6 +398,8 @@ hipError_t launch_deg_H(const DegView& d, const float* x, float* y, int B, int C
             return blur2(d, x, scratch, y, B, C, H, W, +1, 0, nullptr, nullptr, s);
         case DEG_PSF_BLUR: case DEG_PSF_BLUR_ZERO:      // one launch, no scratch (psf.hip)
             return launch_psf2d(d, x, y, B, C, H, W, +1, 0, nullptr, nullptr, s);
+        case DEG_PSF_SR:           // blur and decimate in one launch: K^2 multiply-adds per low-resolution output (psf.hip)
+            return launch_psf_sr(d, x, y, B, C, H, W, +1, 0, nullptr, nullptr, s);
         case DEG_SR_FILTER: {      // y = decimate(filter (*) x)
             if (!scratch || d.ntaps < 1 || d.ntaps > 127 || d.sf <= 0 || H % d.sf || W % d.sf) return hipErrorInvalidValue;
             float* s0 = scratch; float* s1 = scratch + (size_t)B * C * H * W;
@@ -428,6 +430,8 @@ hipError_t launch_deg_Hadj(const DegView& d, const float* y, float* x, int B, in
             return blur2(d, y, scratch, x, B, C, H, W, -1, 0, nullptr, nullptr, s);
         case DEG_PSF_BLUR: case DEG_PSF_BLUR_ZERO:
             return launch_psf2d(d, y, x, B, C, H, W, -1, 0, nullptr, nullptr, s);
+        case DEG_PSF_SR:           // the polyphase adjoint: no zero-filled tensor
+            return launch_psf_sr(d, y, x, B, C, H, W, -1, 0, nullptr, nullptr, s);
         case DEG_SR_FILTER: {      // x = filter^T (*) zerofill(y)
             if (!scratch || d.ntaps < 1 || d.ntaps > 127 || d.sf <= 0 || H % d.sf || W % d.sf) return hipErrorInvalidValue;
             float* s0 = scratch; float* s1 = scratch + (size_t)B * C * H * W;
@@ -521,6 +525,12 @@ hipError_t launch_grad_step(const DegView& d, const float* x, const float* y, co
             hipError_t e = launch_psf2d(d, x, scratch, B, C, H, W, +1, laplace ? 3 : 1, y, nullptr, s);      // scratch = Hx - y  (or its sign)
             if (e != hipSuccess) return e;
             return launch_psf2d(d, scratch, z, B, C, H, W, -1, 2, x, coef, s);                              // z = x - coef*H_adj(scratch)
+        }
+        case DEG_PSF_SR: {         // two applications; scratch: B*C*H*W / sf^2 floats (the low-resolution residual)
+            if (!scratch || !psf_taps_ok(d, H, W)) return hipErrorInvalidValue;
+            hipError_t e = launch_psf_sr(d, x, scratch, B, C, H, W, +1, laplace ? 3 : 1, y, nullptr, s);    // scratch = Hx - y  (or its sign)
+            if (e != hipSuccess) return e;
+            return launch_psf_sr(d, scratch, z, B, C, H, W, -1, 2, x, coef, s);                             // z = x - coef*H_adj(scratch)
         }
         case DEG_SR_FILTER: {
             if (!scratch || d.ntaps < 1 || d.ntaps > 127 || d.sf <= 0 || H % d.sf || W % d.sf) return hipErrorInvalidValue;
@@ -772,7 +782,7 @@ hipError_t launch_ot_ode_vec(const DegView& d, const float* x, const float* vt, 
                              float sigma2, float* vec, int B, int C, int H, int W, hipStream_t s) {
     if (d.kind == DEG_BLUR) return hipErrorInvalidValue;   // Fourier-domain solve: launch_ot_ode_vec_blur (fft2.hip)
     if (d.kind == DEG_BLUR_ZERO) return hipErrorInvalidValue;   // no closed form: launch_krylov_solve (krylov.hip)
-    if (deg_is_psf(d.kind)) return hipErrorInvalidValue;        // DEG_PSF_BLUR: launch_ot_ode_vec_blur; DEG_PSF_BLUR_ZERO: launch_krylov_solve
+    if (deg_is_psf(d.kind)) return hipErrorInvalidValue;        // DEG_PSF_BLUR, DEG_PSF_SR: launch_ot_ode_vec_blur; DEG_PSF_BLUR_ZERO: launch_krylov_solve
     if (d.kind == DEG_SR && (d.sf <= 0 || H % d.sf || W % d.sf)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(ot_ode_vec_kernel, grid_for(C * H * W, B), dim3(256), 0, s, d, x, vt, y, one_minus_t, rt2, sigma2, vec, C, H, W);
     return hipGetLastError();

@@ -52,6 +52,7 @@ __global__ __launch_bounds__(kThreads) void pnpgs_seed4_kernel(const float4* __r
 //   PNPGS_PGD         out = z - alpha Dg                                   (pnp_gs.py:220-222)
 //   PNPGS_HQS_MASK    Dx = z - Dg;  out = M noisy - M Dx + Dx             (:150-156, prox_datafit :33-34 with H = the mask)
 //   PNPGS_HQS_BLUR    Dx = z - Dg;  out = alpha H_adj(noisy) + (0.1 alpha Dx + alpha (1 - 0.1 alpha) z)      (:166-168, prox_datafit :36)
+//   PNPGS_HQS_SR      the same with 0.065 for 0.1                                                           (:189-191; the input of launch_fft_prox_sr)
 template <int MODE>
 __global__ __launch_bounds__(kThreads) void pnpgs_combine4_kernel(const float4* z /* may be `out` */, const float4* __restrict__ N, const float4* __restrict__ JN,
                                                                   const float4* __restrict__ aux, const uchar4* __restrict__ mask,
@@ -61,6 +62,10 @@ __global__ __launch_bounds__(kThreads) void pnpgs_combine4_kernel(const float4* 
     if (MODE == PNPGS_PGD || MODE == PNPGS_HQS_BLUR) {
         const double ad = *alpha_dev;
         a = (float)ad; c1 = (float)(0.1 * ad); c2 = (float)(ad * (1.0 - ad * 0.1));
+    }
+    if (MODE == PNPGS_HQS_SR) {
+        const double ad = *alpha_dev;
+        a = (float)ad; c1 = (float)(0.065 * ad); c2 = (float)(ad * (1.0 - ad * 0.065));
     }
     for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n4; i += (int64_t)gridDim.x * kThreads) {
         const float4 zz = z[i];
@@ -137,8 +142,8 @@ hipError_t launch_pnpgs_combine(int mode, const float* z, const float* N, const 
                                 float* out, int B, int64_t n, int64_t hw, hipStream_t s) {
     if (n % 4 || B <= 0) return hipErrorInvalidValue;
     if (mode == PNPGS_HQS_MASK && (hw % 4 || n % hw || !mask || !aux)) return hipErrorInvalidValue;
-    if (mode == PNPGS_HQS_BLUR && !aux) return hipErrorInvalidValue;
-    if ((mode == PNPGS_PGD || mode == PNPGS_HQS_BLUR) && !alpha_dev) return hipErrorInvalidValue;
+    if ((mode == PNPGS_HQS_BLUR || mode == PNPGS_HQS_SR) && !aux) return hipErrorInvalidValue;
+    if ((mode == PNPGS_PGD || mode == PNPGS_HQS_BLUR || mode == PNPGS_HQS_SR) && !alpha_dev) return hipErrorInvalidValue;
     const int64_t n4 = (int64_t)B * n / 4, img4 = n / 4, hw4 = std::max<int64_t>(hw / 4, 1);
     const dim3 grid(stream_blocks(n4)), block(kThreads);
 #define PNPGS_COMBINE(M) hipLaunchKernelGGL(pnpgs_combine4_kernel<M>, grid, block, 0, s, (const float4*)z, (const float4*)N, (const float4*)JN, \
@@ -148,6 +153,7 @@ hipError_t launch_pnpgs_combine(int mode, const float* z, const float* N, const 
         case PNPGS_PGD: PNPGS_COMBINE(PNPGS_PGD); break;
         case PNPGS_HQS_MASK: PNPGS_COMBINE(PNPGS_HQS_MASK); break;
         case PNPGS_HQS_BLUR: PNPGS_COMBINE(PNPGS_HQS_BLUR); break;
+        case PNPGS_HQS_SR: PNPGS_COMBINE(PNPGS_HQS_SR); break;
         default: return hipErrorInvalidValue;
     }
 #undef PNPGS_COMBINE

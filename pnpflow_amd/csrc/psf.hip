@@ -99,9 +99,194 @@ __global__ __launch_bounds__(256) void psf2d_kernel(const float* __restrict__ in
     }
 }
 
+// ---- DEG_PSF_SR: blur with the PSF, then keep every sf-th sample:  H x [i][j] = (k (*) x)[i sf][j sf]  (circular) -------------------------------
+// The forward kernel computes the K^2 multiply-adds of the LOW-resolution outputs only.  A workgroup owns a tile of SR_TLX x TLY low-resolution outputs and
+// stages their high-resolution neighbourhood, ((TLY - 1) sf + K) rows x ((SR_TLX - 1) sf + K) columns, once, through the same true-modulo index tables as
+// psf2d_kernel.  The staged columns are de-interleaved by their phase px % sf: output column x reads staged column x sf + c for the tap offset c = 2r - kx,
+// i.e. element x + c / sf of phase plane c % sf - neighbouring outputs read neighbouring words, and the taps of one phase (c = p, p + sf, ...) slide a
+// window of SR_NO consecutive outputs along the plane exactly as psf2d_kernel's window slides along a row: one LDS read per tap feeds eight multiply-adds.
+// The tap order is fixed (rows ascending; phases ascending; offsets ascending), one fp32 fmaf chain per output, taps through the scalar cache.
+constexpr int SR_TLX = 32, SR_NO = 8;
+__global__ __launch_bounds__(256) void psf_sr_fwd_kernel(const float* __restrict__ in, float* __restrict__ out, const float* __restrict__ taps, int K, int sf, int H,
+                                                        int W, int TLY, int mode, const float* __restrict__ aux, const float* __restrict__ coef,
+                                                        int planes_per_image) {
+    constexpr int NO = SR_NO, TLX = SR_TLX;
+    extern __shared__ float s_p[];
+    const int r = K / 2, Hl = H / sf, Wl = W / sf;
+    const int PWX = (TLX - 1) * sf + K, PWY = (TLY - 1) * sf + K, QW = TLX + 2 * r / sf, PITCH = (sf * QW) | 1;
+    float* s_in = s_p;                                         // [PWY][sf][QW], row pitch PITCH
+    int* s_iy = reinterpret_cast<int*>(s_in + PWY * PITCH);    // [PWY] source row of staged row py
+    int* s_ix = s_iy + PWY;                                    // [PWX] source column
+    const int tid = threadIdx.x;
+    const int plane = blockIdx.z, xl0 = blockIdx.x * TLX, yl0 = blockIdx.y * TLY;
+    for (int i = tid; i < PWY + PWX; i += 256) {
+        const bool col = i >= PWY;
+        const int N = col ? W : H;
+        int g = (col ? xl0 * sf + i - PWY : yl0 * sf + i) - r;
+        g %= N; g += g < 0 ? N : 0;
+        s_iy[i] = g;                                           // (s_ix follows s_iy)
+    }
+    __syncthreads();
+    const float* src = in + (size_t)plane * H * W;
+    for (int i = tid; i < PWY * PWX; i += 256) {
+        const int py = i / PWX, px = i - py * PWX;
+        const int q = px / sf;
+        s_in[py * PITCH + (px - q * sf) * QW + q] = src[(size_t)s_iy[py] * W + s_ix[px]];
+    }
+    __syncthreads();
+    const int y = tid / (TLX / NO), x = (tid - y * (TLX / NO)) * NO;
+    if (y >= TLY || yl0 + y >= Hl) return;
+    float a[NO], w[NO];
+#pragma unroll
+    for (int j = 0; j < NO; ++j) a[j] = 0.f;
+    // convolution: out[y][x + j] = sum g[ky][kx] in[y sf + 2r - ky][(x + j) sf + 2r - kx]
+    for (int ky = 0; ky < K; ++ky) {
+        const float* row = s_in + (y * sf + 2 * r - ky) * PITCH + x;
+        const float* g = taps + ky * K + 2 * r;
+        for (int p = 0; p < sf && p <= 2 * r; ++p) {
+            const float* pl = row + p * QW;
+            const int nq = (2 * r - p) / sf + 1;               // offsets c = p + sf q <= 2r, tap column kx = 2r - c
+#pragma unroll
+            for (int j = 0; j < NO - 1; ++j) w[j] = pl[j];
+            for (int q = 0; q < nq; ++q) {
+                w[NO - 1] = pl[q + NO - 1];                    // <= element TLX - 1 + (2r - p) / sf of the plane: staged
+                const float gk = g[-(p + sf * q)];
+#pragma unroll
+                for (int j = 0; j < NO; ++j) a[j] = fmaf(gk, w[j], a[j]);
+#pragma unroll
+                for (int j = 0; j < NO - 1; ++j) w[j] = w[j + 1];
+            }
+        }
+    }
+    const int b = plane / planes_per_image;
+#pragma unroll
+    for (int j = 0; j < NO; ++j) {
+        if (xl0 + x + j >= Wl) break;
+        float v = a[j];
+        const size_t o = ((size_t)plane * Hl + yl0 + y) * Wl + xl0 + x + j;
+        if (mode == 1) v = v - aux[o];
+        else if (mode == 2) v = aux[o] - coef[b] * v;
+        else if (mode == 3) v = (v - aux[o]) > 0.f ? 1.f : -1.f;
+        out[o] = v;
+    }
+}
+
+// The adjoint in its polyphase form: H_adj y [m][n] = sum over the taps (ky, kx) with m + ky - r = 0 and n + kx - r = 0 (mod sf) of
+// g[ky][kx] y[(m + ky - r) / sf][(n + kx - r) / sf] - the zero-filled tensor is never formed, and an output sums only the <= ceil(K / sf)^2 taps of its phase
+// (m mod sf, n mod sf).  A workgroup owns a high-resolution tile of 16 sf rows x 32 sf columns and stages the low-resolution patch under it (wrap through index
+// tables, true modulo on the low-resolution grid).  The outputs of one phase form a 16 x 32 grid on which the phase's taps are a plain correlation of the patch:
+// a wave takes one phase at a time (so its taps are uniform: scalar cache), a lane eight consecutive outputs of the phase with the sliding window.
+constexpr int SRA_GX = 32, SRA_GY = 16;
+__global__ __launch_bounds__(256) void psf_sr_adj_kernel(const float* __restrict__ in, float* __restrict__ out, const float* __restrict__ taps, int K, int sf, int H,
+                                                        int W, int mode, const float* __restrict__ aux, const float* __restrict__ coef, int planes_per_image) {
+    constexpr int NO = SR_NO, GX = SRA_GX, GY = SRA_GY;
+    static_assert(GY * (GX / NO) == 64, "one wave per phase");
+    extern __shared__ float s_p[];
+    const int r = K / 2, Hl = H / sf, Wl = W / sf;
+    const int RL = r / sf, RU = (r + sf - 1) / sf;             // low-resolution rows / columns needed before and after the tile's own
+    const int PWX = GX + RL + RU, PWY = GY + RL + RU, PWP = PWX | 1;
+    float* s_in = s_p;                                         // [PWY][PWP]
+    int* s_iy = reinterpret_cast<int*>(s_in + PWY * PWP);
+    int* s_ix = s_iy + PWY;
+    const int tid = threadIdx.x;
+    const int plane = blockIdx.z, xl0 = blockIdx.x * GX, yl0 = blockIdx.y * GY;
+    for (int i = tid; i < PWY + PWX; i += 256) {
+        const bool col = i >= PWY;
+        const int N = col ? Wl : Hl;
+        int g = (col ? xl0 + i - PWY : yl0 + i) - RL;
+        g %= N; g += g < 0 ? N : 0;
+        s_iy[i] = g;
+    }
+    __syncthreads();
+    const float* src = in + (size_t)plane * Hl * Wl;
+    for (int i = tid; i < PWY * PWX; i += 256) {
+        const int py = i / PWX, px = i - py * PWX;
+        s_in[py * PWP + px] = src[(size_t)s_iy[py] * Wl + s_ix[px]];
+    }
+    __syncthreads();
+    const int b = plane / planes_per_image;
+    const int wave = tid >> 6, lane = tid & 63;
+    const int ay = lane / (GX / NO), ax = (lane - ay * (GX / NO)) * NO;
+    for (int ph = wave; ph < sf * sf; ph += 4) {
+        const int py = ph / sf, px = ph - py * sf;
+        // first tap of the phase and the patch offset it reads: ky0 = (r - py) mod sf, rows ay + oy + a for the taps ky0 + sf a
+        int ky0 = (r - py) % sf; ky0 += ky0 < 0 ? sf : 0;
+        int kx0 = (r - px) % sf; kx0 += kx0 < 0 ? sf : 0;
+        const int ny = ky0 < K ? (K - 1 - ky0) / sf + 1 : 0, nx = kx0 < K ? (K - 1 - kx0) / sf + 1 : 0;
+        const int oy = (py + ky0 - r) / sf + RL, ox = (px + kx0 - r) / sf + RL;      // exact divisions; >= 0 after + RL
+        float a[NO], w[NO];
+#pragma unroll
+        for (int j = 0; j < NO; ++j) a[j] = 0.f;
+        for (int ta = 0; ta < ny; ++ta) {
+            const float* row = s_in + (ay + oy + ta) * PWP + ax + ox;
+            const float* g = taps + (ky0 + sf * ta) * K + kx0;
+#pragma unroll
+            for (int j = 0; j < NO - 1; ++j) w[j] = row[j];
+            for (int tb = 0; tb < nx; ++tb) {
+                w[NO - 1] = row[tb + NO - 1];                  // column ax + ox + tb + NO - 1 <= GX - 1 + RL + RU of the patch
+                const float gk = g[sf * tb];
+#pragma unroll
+                for (int j = 0; j < NO; ++j) a[j] = fmaf(gk, w[j], a[j]);
+#pragma unroll
+                for (int j = 0; j < NO - 1; ++j) w[j] = w[j + 1];
+            }
+        }
+        const int m = (yl0 + ay) * sf + py;
+        if (m >= H) continue;
+#pragma unroll
+        for (int j = 0; j < NO; ++j) {
+            const int n = (xl0 + ax + j) * sf + px;
+            if (n >= W) break;
+            float v = a[j];
+            const size_t o = ((size_t)plane * H + m) * W + n;
+            if (mode == 1) v = v - aux[o];
+            else if (mode == 2) v = aux[o] - coef[b] * v;
+            else if (mode == 3) v = (v - aux[o]) > 0.f ? 1.f : -1.f;
+            out[o] = v;
+        }
+    }
+}
+
 bool psf_taps_ok(const DegView& d, int H, int W) {
     if (!d.taps || d.ntaps < 1 || d.ntaps > PSF_MAX_SIDE || !(d.ntaps & 1)) return false;
+    if (d.kind == DEG_PSF_SR) return d.sf >= 1 && d.sf <= PSF_SR_MAX_SF && H % d.sf == 0 && W % d.sf == 0 && d.ntaps <= std::min(H, W);
     return d.kind == DEG_PSF_BLUR_ZERO || (d.kind == DEG_PSF_BLUR && d.ntaps <= std::min(H, W));      // the circular filter must hold the kernel
+}
+
+// rows of low-resolution outputs per workgroup of psf_sr_fwd_kernel and the LDS they need: 64 rows (one per thread row) while the staged neighbourhood
+// fits 64 KB; a large sf x K product takes up to 160 KB before the tile drops under 16 rows
+static size_t psf_sr_fwd_lds(int K, int sf, int TLY) {
+    const int PWX = (SR_TLX - 1) * sf + K, PWY = (TLY - 1) * sf + K, QW = SR_TLX + 2 * (K / 2) / sf, PITCH = (sf * QW) | 1;
+    return ((size_t)PWY * PITCH + PWY + PWX) * sizeof(float);
+}
+static int psf_sr_fwd_rows(int K, int sf, int Hl) {
+    auto fit = [&](size_t budget) { int t = std::min(256 / (SR_TLX / SR_NO), std::max(Hl, 1)); while (t > 1 && psf_sr_fwd_lds(K, sf, t) > budget) --t; return t; };
+    const int t = fit(64 * 1024);
+    return (t >= 16 || t >= Hl) ? t : fit(160 * 1024);
+}
+
+// one application of DEG_PSF_SR in one launch, no scratch: sign +1 = H ([H][W] -> [H / sf][W / sf]), -1 = H_adj; mode / aux / coef as launch_psf2d, on the
+// OUTPUT's grid
+hipError_t launch_psf_sr(const DegView& d, const float* in, float* out, int B, int C, int H, int W, int sign, int mode, const float* aux, const float* coef,
+                         hipStream_t s) {
+    if (!in || !out || in == out || B <= 0 || C <= 0 || H <= 0 || W <= 0 || (int64_t)B * C > 65535 || d.kind != DEG_PSF_SR || !psf_taps_ok(d, H, W)) return hipErrorInvalidValue;
+    if ((mode != 0 && !aux) || (mode == 2 && !coef)) return hipErrorInvalidValue;
+    const int K = d.ntaps, sf = d.sf, Hl = H / sf, Wl = W / sf;
+    if (sign > 0) {
+        const int TLY = psf_sr_fwd_rows(K, sf, Hl);
+        const size_t lds = psf_sr_fwd_lds(K, sf, TLY);
+        if (lds > 160 * 1024) return hipErrorInvalidValue;
+        static unsigned long long attr = 0ull;
+        if (lds > 64 * 1024) { hipError_t e = set_max_dynamic_lds_once(reinterpret_cast<const void*>(psf_sr_fwd_kernel), attr, 160 * 1024); if (e != hipSuccess) return e; }
+        hipLaunchKernelGGL(psf_sr_fwd_kernel, dim3((Wl + SR_TLX - 1) / SR_TLX, (Hl + TLY - 1) / TLY, B * C), dim3(256), lds, s, in, out, d.taps, K, sf, H, W, TLY, mode,
+                           aux, coef, C);
+    } else {
+        const int r = K / 2, RL = r / sf, RU = (r + sf - 1) / sf, PWX = SRA_GX + RL + RU, PWY = SRA_GY + RL + RU;
+        const size_t lds = ((size_t)PWY * (PWX | 1) + PWY + PWX) * sizeof(float);        // <= 31 KB at K = 63, sf = 1
+        hipLaunchKernelGGL(psf_sr_adj_kernel, dim3((Wl + SRA_GX - 1) / SRA_GX, (Hl + SRA_GY - 1) / SRA_GY, B * C), dim3(256), lds, s, in, out, d.taps, K, sf, H, W, mode,
+                           aux, coef, C);
+    }
+    return hipGetLastError();
 }
 
 // one application; sign +1 = H, -1 = H_adj (the zero-boundary kind turns it round, like blur2)

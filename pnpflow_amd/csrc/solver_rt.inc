@@ -98,8 +98,8 @@ static int graph_stream(pf_engine* e, bool need, hipStream_t& s) {
 // the operator rules D-Flow and Flow-Priors share (`who`: the prefix of their messages); Hy: the side of the measurement
 static int check_operator(pf_engine* e, const char* who, const pf_degradation* d, int H, int& Hy) {
     const std::string p = std::string(who) + ": ";
-    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_PSF_BLUR_ZERO) { e->err = p + "unknown degradation kind"; return PF_ERR_INVALID; }
-    const bool sr = d->kind == PF_DEG_SUPERRESOLUTION || d->kind == PF_DEG_SR_FILTERED;
+    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_PSF_SR) { e->err = p + "unknown degradation kind"; return PF_ERR_INVALID; }
+    const bool sr = deg_is_sr(d->kind);
     if (sr && (d->sf <= 0 || H % d->sf)) { e->err = p + "superresolution factor must divide the image size"; return PF_ERR_INVALID; }
     if ((d->kind == PF_DEG_GAUSSIAN_BLUR || d->kind == PF_DEG_GAUSSIAN_BLUR_ZERO || d->kind == PF_DEG_SR_FILTERED) && (!d->taps || d->ntaps < 1 || d->ntaps > 127)) {
         e->err = p + "the filtered operators need 1..127 device taps"; return PF_ERR_INVALID;

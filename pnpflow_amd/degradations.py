@@ -27,8 +27,8 @@ class Degradation:
         raise NotImplementedError()
 
     def out_side(self, side):
-        """Side of H's output for an input of side `side`: the two superresolution kinds decimate by sf."""
-        return side // (getattr(self, "sf", 1) if self.kind in (_lib.PF_DEG_SUPERRESOLUTION, _lib.PF_DEG_SR_FILTERED) else 1)
+        """Side of H's output for an input of side `side`: the superresolution kinds decimate by sf."""
+        return side // (getattr(self, "sf", 1) if self.kind in (_lib.PF_DEG_SUPERRESOLUTION, _lib.PF_DEG_SR_FILTERED, _lib.PF_DEG_PSF_SR) else 1)
 
     # -- engine side -----------------------------------------------------------------------
     def descriptor(self, B, H, W, device):
@@ -48,7 +48,7 @@ class Degradation:
             out = torch.empty((B, Cc, self.out_side(Hf), self.out_side(Wf)), dtype=torch.float32, device=x.device)
         if B == 0:
             return out          # an empty shard (global batch smaller than the number of ranks): nothing to launch
-        # (the point-spread-function kinds apply in one launch and need no scratch)
+        # (the point-spread-function kinds, PF_DEG_PSF_SR included, apply in one launch and need no scratch)
         n_scr = {_lib.PF_DEG_GAUSSIAN_BLUR: 1, _lib.PF_DEG_GAUSSIAN_BLUR_ZERO: 1, _lib.PF_DEG_SR_FILTERED: 2}.get(self.kind, 0)
         scratch = torch.empty((n_scr, B, Cc, Hf, Wf), dtype=torch.float32, device=x.device) if n_scr else None
         fn = lib.pf_degradation_H_adj if adjoint else lib.pf_degradation_H
@@ -310,9 +310,13 @@ class Superresolution(Degradation):
 
 
 def __getattr__(name):
-    """`degradations.PSFDeblurring` (the blur with any 2-D point-spread function) is defined in psf_deblurring.py, which imports this module's
-    Degradation, and is resolved on first use: this module's own namespace holds the reference's operator classes only."""
+    """`degradations.PSFDeblurring` (the blur with any 2-D point-spread function) and `degradations.PSFSuperresolution` (that blur, then decimation) are
+    defined in psf_deblurring.py / psf_superresolution.py, which import this module's Degradation, and are resolved on first use: this module's own
+    namespace holds the reference's operator classes only."""
     if name == "PSFDeblurring":
         from .psf_deblurring import PSFDeblurring
         return PSFDeblurring
+    if name == "PSFSuperresolution":
+        from .psf_superresolution import PSFSuperresolution
+        return PSFSuperresolution
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -5,6 +5,13 @@ forward with autograd graph and an input-gradient backward (ot_ode.py:71-147).  
 retained forward + the hand-written backward of the engine (pf_unet_forward_retain /
 pf_unet_backward) replace the two forwards + autograd; the closed-form solve and the Euler
 update are HIP pointwise kernels (pf_ot_ode_vec / pf_ot_ode_update).
+
+Which solve a problem takes on the engine loop (pf_ot_ode_restore):
+    denoising, inpainting, random_inpainting, paintbrush_inpainting, superresolution    per pixel, closed form
+    gaussian_deblurring_FFT, psf_deblurring_FFT                                         Fourier solve on the image grid
+    superresolution_blur, superresolution_bicubic (blur, then decimate)                 Fourier solve on the low-resolution grid, where H H^T is circulant
+                                                                                        (the reference has no branch for them and runs its GMRES)
+    gaussian_deblurring, psf_deblurring (zero boundary)                                 batched GMRES on the device
 """
 from __future__ import annotations
 
@@ -60,7 +67,10 @@ class OT_ODE(Solver):
         # the reference's generic branch for it with the batched GMRES on the device (pf_krylov_solve inside pf_ot_ode_restore)
         # (the point-spread-function kinds are the Gaussian blurs' twins: PF_DEG_PSF_BLUR takes the Fourier solve, PF_DEG_PSF_BLUR_ZERO the Krylov one)
         krylov = getattr(degradation, "kind", None) in (_lib.PF_DEG_GAUSSIAN_BLUR_ZERO, _lib.PF_DEG_PSF_BLUR_ZERO)
-        if not krylov and problem not in ("denoising", "inpainting", "random_inpainting", "paintbrush_inpainting", "superresolution", "gaussian_deblurring_FFT",
+        # blur, then decimate (PF_DEG_SR_FILTERED, PF_DEG_PSF_SR; problems superresolution_bicubic / superresolution_blur): H H^T is circulant on the low-resolution
+        # grid, so the engine solves the generic branch's system exactly with one Fourier solve there, where the reference runs its GMRES
+        sr_fourier = getattr(degradation, "kind", None) in (_lib.PF_DEG_SR_FILTERED, _lib.PF_DEG_PSF_SR)
+        if not krylov and not sr_fourier and problem not in ("denoising", "inpainting", "random_inpainting", "paintbrush_inpainting", "superresolution", "gaussian_deblurring_FFT",
                                           "psf_deblurring_FFT"):
             # OUT OF THE SURVEY 8 HOT-PATH SCOPE (unreachable for the five problems of main.py's table; kept from round 2,
             # host-orchestrated, golden-pinned, not part of any coverage claim): any other problem name takes the reference's generic

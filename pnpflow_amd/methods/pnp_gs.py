@@ -2,12 +2,20 @@
 al., 2022).
 
 `model` is a GRADIENT_STEP_DENOISER (pnpflow_amd/train_denoiser.py).  Every iteration needs Dg = (z - N) - J_N(z)^T (z - N) at some
-point z and denoiser level, then one of three closed forms:
+point z and denoiser level, then one of four closed forms:
 
     algo pgd                             z = x - lr grad_datafit(x) (not for gaussian denoising);  x = z - alpha Dg(z)
     algo hqs, random_inpainting          Dx = x - Dg(x);  x = H(y) - H(Dx) + Dx  (the last iteration leaves x as it is)
     algo hqs, gaussian_deblurring_FFT    Fourier-domain prox of 0.1 alpha Dx + alpha (1 - 0.1 alpha) x, then alpha *= 0.9 when the
                                          objective gap falls below 0.1 / alpha |x_new - x|^2
+    algo hqs, superresolution_blur /     z = 0.065 alpha Dx + alpha (1 - 0.065 alpha) x, then the exact prox of alpha/2 |H x - y|^2 at z; the denoiser
+              superresolution_bicubic    level is 2 sigma_noise, alpha never decays (the schedule of the reference's branch, pnp_gs.py:180-200)
+
+The reference's own prox_datafit for superresolution_bicubic (pnp_gs.py:45-76; main.py cannot reach it) is not a proximal map: its `below` multiplies
+the aliased power spectrum by the data spectrum (:71-72).  What is built instead is exact.  For circular H = S K (blur, keep every sf-th sample)
+H H^T is circulant on the low-resolution grid with the eigenvalues lam[u, v] = 1/sf^2 sum_{a, b < sf} |fft2 k|^2 [u + a H/sf, v + b W/sf], so by the
+Woodbury identity  prox(z) = r - alpha H_adj( ifft2_l( fft2_l(H r) / (alpha lam + 1) ) ),  r = z + alpha H_adj(y):  one Fourier solve on the
+low-resolution grid between one H and one H_adj (pf_sr_prox).
 
 The whole loop of a batch is one engine call (pf_pnp_gs_restore): retained forward, seed, hand-written backward and the fused combine
 per iteration, replayed as one hipGraph; alpha lives on the device.
@@ -24,8 +32,9 @@ from . import _harness
 from ._harness import IterCallback, Solver
 
 SUPPORTED = ("algo pgd (any problem, gaussian or laplace noise), algo hqs with problem random_inpainting, algo hqs with problem gaussian_deblurring_FFT "
-             "or psf_deblurring_FFT")
+             "or psf_deblurring_FFT, algo hqs with problem superresolution_blur or superresolution_bicubic")
 FFT_BLURS = ("gaussian_deblurring_FFT", "psf_deblurring_FFT")      # the circular blurs: hqs has a Fourier-domain prox for them
+SR_BLURS = ("superresolution_blur", "superresolution_bicubic")     # circular blur, then decimation: the same on the low-resolution grid
 
 
 class PROX_PNP(Solver):
@@ -43,7 +52,7 @@ class PROX_PNP(Solver):
             return self.model(x, sigma)
 
     def prox_datafit(self, x, y, H, H_adj, degradation=None, alpha=None):
-        """pnp_gs.py:32-44 (the unreachable superresolution_bicubic branch is not implemented)."""
+        """pnp_gs.py:32-44; for the blur-then-decimate problems the exact prox (module docstring) in place of the reference's :45-76."""
         if self.args.noise_type == 'gaussian' and self.args.problem == "random_inpainting":
             return H(y) - H(x) + x
         if self.args.noise_type == 'gaussian' and self.args.problem in FFT_BLURS:
@@ -51,6 +60,13 @@ class PROX_PNP(Solver):
             fft_kernel = torch.fft.fft2(degradation.filter.to(x.device))
             inv = alpha * torch.conj(fft_kernel) * fft_kernel + 1.
             return torch.real(torch.fft.ifft2(fft_d / inv))
+        if self.args.noise_type == 'gaussian' and self.args.problem in SR_BLURS:
+            r = x + alpha * H_adj(y)
+            k2 = torch.fft.fft2(degradation.filter.to(x.device)).abs() ** 2
+            sf, Hl, Wl = degradation.sf, x.shape[-2] // degradation.sf, x.shape[-1] // degradation.sf
+            lam = k2.reshape(*k2.shape[:2], sf, Hl, sf, Wl).sum(dim=(2, 4)) / sf ** 2
+            sol = torch.real(torch.fft.ifft2(torch.fft.fft2(H(r)) / (alpha * lam + 1.)))
+            return r - alpha * H_adj(sol)
         raise NotImplementedError(f"prox_datafit: no closed form for problem {self.args.problem!r} with {self.args.noise_type} noise")
 
     def objective(self, x, y, H, H_adj, lmbda, g):
@@ -62,7 +78,7 @@ class PROX_PNP(Solver):
 
     # ---- host schedule ---------------------------------------------------------------------------------------------------------
     def algo_code(self):
-        """0 pgd | 1 hqs random_inpainting | 2 hqs gaussian_deblurring_FFT / psf_deblurring_FFT.  The reference's loop matches no branch for any other
+        """0 pgd | 1 hqs random_inpainting | 2 hqs gaussian_deblurring_FFT / psf_deblurring_FFT | 3 hqs superresolution_blur / superresolution_bicubic.  The reference's loop matches no branch for any other
         pair and silently returns the initialisation; here that is an error."""
         algo, problem = self.args.algo, self.args.problem
         if algo == "pgd":
@@ -71,6 +87,8 @@ class PROX_PNP(Solver):
             return 1
         if algo == "hqs" and problem in FFT_BLURS:
             return 2
+        if algo == "hqs" and problem in SR_BLURS:
+            return 3
         if algo == "hqs" and problem in ("gaussian_deblurring", "psf_deblurring"):
             raise ValueError(f"pnp_gs: algo 'hqs' has no form for problem {problem!r} (the zero-boundary blur): its prox is a Fourier solve of the "
                              f"circular operator (problem '{problem}_FFT'); use algo 'pgd'")
@@ -83,6 +101,8 @@ class PROX_PNP(Solver):
             tab = [0.2 if it < 20 else sigma_noise for it in range(n)]
         elif code == 2:
             tab = [1.8 * sigma_noise] * n
+        elif code == 3:
+            tab = [2.0 * sigma_noise] * n          # pnp_gs.py:182-183
         else:
             tab = [self.args.sigma_factor * sigma_noise] * n
         return np.asarray(tab, dtype=np.float32)

@@ -9,6 +9,28 @@ from . import _lib
 from .degradations import Degradation
 
 
+def sanitise_kernel(kernel, who):
+    """A real, finite 2-D kernel with odd sides <= 63 -> (square fp32 taps, side): a rectangular kernel is zero-padded, centred, to a square, and
+    all-zero border rings are cropped (no non-zero tap is dropped, the centre stays the centre).  `who` prefixes the error messages."""
+    k = np.asarray(kernel.detach().cpu().numpy() if isinstance(kernel, torch.Tensor) else kernel)
+    if k.ndim != 2 or k.size == 0 or np.iscomplexobj(k) or not np.issubdtype(k.dtype, np.number):
+        raise ValueError(f"{who}: the kernel must be a real 2-D array, got shape {k.shape} dtype {k.dtype}")
+    k = k.astype(np.float32)
+    if not np.isfinite(k).all():
+        raise ValueError(f"{who}: the kernel has non-finite taps")
+    if k.shape[0] % 2 == 0 or k.shape[1] % 2 == 0:
+        raise ValueError(f"{who}: both sides of the kernel must be odd (its centre is a tap), got {k.shape}")
+    if max(k.shape) > _lib.PSF_MAX_SIDE:
+        raise ValueError(f"{who}: kernel sides are limited to {_lib.PSF_MAX_SIDE}, got {k.shape}")
+    K = max(k.shape)
+    sq = np.zeros((K, K), dtype=np.float32)
+    oy, ox = (K - k.shape[0]) // 2, (K - k.shape[1]) // 2
+    sq[oy:oy + k.shape[0], ox:ox + k.shape[1]] = k
+    while K > 1 and not (sq[0].any() or sq[-1].any() or sq[:, 0].any() or sq[:, -1].any()):
+        sq, K = sq[1:-1, 1:-1], K - 2
+    return np.ascontiguousarray(sq), K
+
+
 class PSFDeblurring(Degradation):
     """Blur with any real 2-D point-spread function: what the reference computes when GaussianDeblurring's `.kernel` / `.filter` hold the
     PSF (degradations.py:55-89).  mode 'fft': the circular convolution, H_adj the circular correlation (PF_DEG_PSF_BLUR).  Any other
@@ -20,22 +42,7 @@ class PSFDeblurring(Degradation):
 
     def __init__(self, kernel, mode="fft", num_channels=3, dim_image=128, device="cuda"):
         super().__init__()
-        k = np.asarray(kernel.detach().cpu().numpy() if isinstance(kernel, torch.Tensor) else kernel)
-        if k.ndim != 2 or k.size == 0 or np.iscomplexobj(k) or not np.issubdtype(k.dtype, np.number):
-            raise ValueError(f"PSFDeblurring: the kernel must be a real 2-D array, got shape {k.shape} dtype {k.dtype}")
-        k = k.astype(np.float32)
-        if not np.isfinite(k).all():
-            raise ValueError("PSFDeblurring: the kernel has non-finite taps")
-        if k.shape[0] % 2 == 0 or k.shape[1] % 2 == 0:
-            raise ValueError(f"PSFDeblurring: both sides of the kernel must be odd (its centre is a tap), got {k.shape}")
-        if max(k.shape) > _lib.PSF_MAX_SIDE:
-            raise ValueError(f"PSFDeblurring: kernel sides are limited to {_lib.PSF_MAX_SIDE}, got {k.shape}")
-        K = max(k.shape)
-        sq = np.zeros((K, K), dtype=np.float32)
-        oy, ox = (K - k.shape[0]) // 2, (K - k.shape[1]) // 2
-        sq[oy:oy + k.shape[0], ox:ox + k.shape[1]] = k
-        while K > 1 and not (sq[0].any() or sq[-1].any() or sq[:, 0].any() or sq[:, -1].any()):
-            sq, K = sq[1:-1, 1:-1], K - 2
+        sq, K = sanitise_kernel(kernel, "PSFDeblurring")
         if mode == "fft" and K > dim_image:
             raise ValueError(f"PSFDeblurring(mode='fft'): the {K} x {K} kernel does not fit the {dim_image} x {dim_image} filter")
         self.kind = _lib.PF_DEG_PSF_BLUR if mode == "fft" else _lib.PF_DEG_PSF_BLUR_ZERO

@@ -266,7 +266,7 @@ def compute_psnr(clean_img, noisy_img, rec_img, args, H_adj, iter='final'):
     dev = rec_img.device
     clean = clean_img.to(dev)
     noisy = noisy_img.to(dev)
-    if args.problem in ('superresolution', 'superresolution_bicubic'):
+    if args.problem in ('superresolution', 'superresolution_bicubic', 'superresolution_blur'):
         # the reference post-processes the measurement BEFORE H_adj and the result again (utils.py:598-607);
         # psnr_per_image applies the outer postprocess itself
         noisy = H_adj(postprocess(noisy))
@@ -282,7 +282,7 @@ def compute_ssim(clean_img, noisy_img, rec_img, args, H_adj, iter='final'):
     dev = rec_img.device
     clean = clean_img.to(dev)
     noisy = noisy_img.to(dev)
-    if args.problem in ('superresolution', 'superresolution_bicubic'):
+    if args.problem in ('superresolution', 'superresolution_bicubic', 'superresolution_blur'):
         noisy = H_adj(noisy)                      # single postprocess here (utils.py:782-783)
     ssim_rec = _global_mean(ssim_per_image(rec_img, clean))
     ssim_noisy = _global_mean(ssim_per_image(noisy, clean))
@@ -355,7 +355,7 @@ def save_images(clean_img, noisy_img, rec_img, args, H_adj, iter='final'):
     if getattr(args, 'eval_split', None) == 'test' and ((args.batch < 8 and args.method == 'd_flow') or args.batch < 4):
         psnr = lambda a, b: float(10.0 * np.log10(1.0 / np.mean((a.astype(np.float64) - b.astype(np.float64)) ** 2)))   # skimage's, data_range 1
         for i in range(clean.shape[0]):
-            measured = hadj_ones[i] if args.problem in ('superresolution', 'superresolution_bicubic') else noisy[i]   # (sic: H_adj of ones, utils.py:436,509-511)
+            measured = hadj_ones[i] if args.problem in ('superresolution', 'superresolution_bicubic', 'superresolution_blur') else noisy[i]   # (sic: H_adj of ones, utils.py:436,509-511)
             p_noisy, p_rec = psnr(clean[i], measured), psnr(clean[i], rec[i])
             stem = os.path.join(args.save_path_ip, f"{args.problem}_")
             targets = []
@@ -407,7 +407,7 @@ def compute_lpips(clean_img, noisy_img, rec_img, args, H_adj, iter='final'):
             raise FileNotFoundError("LPIPS weights (torchvision alexnet-owt-*.pth + lpips weights/v0.1/alex.pth) not found; set PNPFLOW_LPIPS_DIR")
         return None
     clean = postprocess(clean_img.to(dev).clone()); noisy = postprocess(noisy_img.to(dev).clone()); rec = postprocess(rec_img.clone())
-    if args.problem in ('superresolution', 'superresolution_bicubic'):
+    if args.problem in ('superresolution', 'superresolution_bicubic', 'superresolution_blur'):
         noisy = postprocess(H_adj(noisy))
     clean, rec, noisy = 2 * clean - 1, 2 * rec - 1, 2 * noisy - 1
     lp_rec = _global_mean(model(clean, rec, normalize=True))
