@@ -142,20 +142,32 @@ typedef enum pf_degradation_kind {
                                    degradations.py:97-127; uses sf, ntaps (4*sf, even), taps */
     PF_DEG_GAUSSIAN_BLUR_ZERO = 6,/* GaussianDeblurring, any mode but "fft" (degradations.py:72-76, 82-86): F.conv2d(padding='same'), i.e. the
                                    correlation with outer(taps, taps) where samples outside the image are 0; H_adj is the matching convolution
-                                   (= H for the symmetric Gaussian).  Same fields as GAUSSIAN_BLUR (ntaps, taps); no ntaps < H restriction */
+                                   (= H for the symmetric Gaussian).  Same fields as GAUSSIAN_BLUR (ntaps, taps) */
     PF_DEG_PSF_BLUR = 7,        /* circular blur with any square 2-D point-spread function (what the reference computes when GaussianDeblurring's
                                    `.filter` holds the PSF, degradations.py:62-89): H is the circular convolution y[i] = sum_j k[j] x[i - (j - r)],
-                                   r = K/2 on both axes, H_adj the circular correlation.  ntaps = K, the side of the K x K PSF: odd, 1 <= K <= 63,
-                                   K <= min(H, W) (the filter must hold the kernel); taps: device [K][K] row-major */
+                                   r = K/2 on both axes, H_adj the circular correlation.  ntaps = K, the side of the K x K PSF; taps: device [K][K] row-major */
     PF_DEG_PSF_BLUR_ZERO = 8,   /* the same PSF where samples outside the image are 0: H is the correlation (F.conv2d(padding='same')), H_adj the
                                    convolution - the true adjoint, which the reference's own spatial H_adj is not for an asymmetric kernel.
-                                   Same fields as PSF_BLUR; no size rule.  Both PSF kinds: an even K, K > 63 or NULL taps returns PF_ERR_INVALID */
+                                   Same fields as PSF_BLUR */
     PF_DEG_PSF_SR = 9           /* superresolution through a blur kernel, y = (k (*) x) decimated by sf: H is the circular convolution of PSF_BLUR sampled at
                                    (i sf, j sf), H_adj the zero-fill followed by the circular correlation - what the reference's Superresolution(mode="bicubic")
-                                   computes when its `.filter` holds the PSF (degradations.py:113-127).  sf: 1 .. 8, dividing H and W; ntaps = K odd, 1 .. 63,
-                                   K <= min(H, W); taps: device [K][K].  Anything else (also x == y) returns PF_ERR_INVALID on every entry point, before a launch.
+                                   computes when its `.filter` holds the PSF (degradations.py:113-127).  Fields: sf, ntaps = K, taps: device [K][K]; x == y is refused.
                                    H H^T is circulant on the low-resolution grid (pf_sr_aliased_spectrum), which gives OT-ODE and the hqs prox one Fourier solve */
 } pf_degradation_kind;
+
+/* When a descriptor may be applied to [B,C,H,W] images.  Every entry point that takes a pf_degradation checks these rules on the host and returns
+ * PF_ERR_INVALID before anything is launched (the solvers: with a pf_last_error text under their prefix, before anything is allocated):
+ *
+ *   any kind                                    0 <= kind <= 9
+ *   MASK_INPAINTING                             mask != NULL
+ *   SUPERRESOLUTION, SR_FILTERED, PSF_SR        sf >= 1, H % sf == 0, W % sf == 0
+ *   GAUSSIAN_BLUR, SR_FILTERED,                 taps != NULL, 1 <= ntaps <= 127; no rule between ntaps and the image side
+ *     GAUSSIAN_BLUR_ZERO
+ *   PSF_BLUR, PSF_BLUR_ZERO, PSF_SR             taps != NULL, K = ntaps odd, 1 <= K <= 63; PSF_BLUR and PSF_SR: K <= min(H, W) (the circular filter
+ *                                               must hold the kernel); PSF_SR: sf <= 8
+ *
+ * The Fourier solves (pf_ot_ode_vec and pf_ot_ode_restore with GAUSSIAN_BLUR, PSF_BLUR, SR_FILTERED or PSF_SR; pf_sr_aliased_spectrum, pf_sr_prox) also need
+ * H, W <= 2048 and, for the separable filters, ntaps <= min(H, W).  What a single solver asks beyond this is written at its entry point. */
 
 typedef struct pf_degradation {
     int32_t kind;

@@ -212,13 +212,6 @@ struct DeviceGuard {
         }                                                                                      \
     } while (0)
 
-static const char* const PSF_TAPS_RULE = "the point-spread-function kinds need a device [K][K] taps array with K odd, 1 .. 63, and K <= the image side for the circular kinds; PF_DEG_PSF_SR also needs sf in 1 .. 8 dividing the image side";
-
-static DegView to_view(const pf_degradation* d) {
-    DegView v{}; v.kind = d->kind; v.half = d->half_size_mask; v.sf = d->sf; v.ntaps = d->ntaps; v.mask = d->mask; v.taps = d->taps;
-    return v;
-}
-
 #include "solver_rt.inc"
 
 // --------------------------------------------------------------------------------------
@@ -1646,10 +1639,11 @@ int pf_unet_vjp(pf_engine* e, const float* x, const float* t, const float* vec, 
 int pf_ot_ode_vec(const pf_degradation* d, const float* x, const float* vt, const float* y, const float* one_minus_t, const float* rt2,
                   float sigma2, float* vec, int B, int C, int H, int W, float* scratch, void* stream) {
     if (!d || !x || !vt || !y || !one_minus_t || !rt2 || !vec) return PF_ERR_INVALID;
-    if (d->kind == PF_DEG_GAUSSIAN_BLUR || d->kind == PF_DEG_PSF_BLUR || d->kind == PF_DEG_PSF_SR || d->kind == PF_DEG_SR_FILTERED) {
-        if (!scratch) return PF_ERR_INVALID;
-        LAUNCHCHK(launch_ot_ode_vec_blur(to_view(d), x, vt, y, one_minus_t, rt2, sigma2, vec, B, C, H, W, scratch, (hipStream_t)stream));
-        return PF_OK;
+    switch (deg_solve(d->kind)) {
+        case DegSolve::FourierSeparable: case DegSolve::FourierPsf: case DegSolve::FourierLowRes:
+            LAUNCHCHK(launch_ot_ode_vec_blur(to_view(d), x, vt, y, one_minus_t, rt2, sigma2, vec, B, C, H, W, scratch, (hipStream_t)stream));
+            return PF_OK;
+        case DegSolve::ClosedForm: case DegSolve::Krylov: break;      // (the Krylov kinds: pf_krylov_solve; the launcher refuses them)
     }
     LAUNCHCHK(launch_ot_ode_vec(to_view(d), x, vt, y, one_minus_t, rt2, sigma2, vec, B, C, H, W, (hipStream_t)stream));
     return PF_OK;
@@ -1805,8 +1799,7 @@ struct SolverBufs {
     int* iter = nullptr;
     DevBufs mem;
     // cached hipGraph of one outer iteration (re-used while the captured arguments stay the same)
-    struct Key { const void* plan; int kind, half, sf, ntaps; const void* mask; const void* taps; const void* noise;
-                 int num_samples, batch_samples, noise_model, B; };
+    struct Key { const void* plan; DegView deg; const void* noise; int num_samples, batch_samples, noise_model, B; };
     static_assert(sizeof(Key) == 4 * sizeof(void*) + 8 * sizeof(int), "SolverBufs::Key is compared with memcmp: it must have no padding bytes");
     CachedGraph graph;
     void reset(pf_engine* e) { graph.drop(e); /* its nodes point into the buffers */ mem.release(e); *this = SolverBufs{}; }
@@ -1876,14 +1869,13 @@ int pf_pnp_flow_restore(pf_engine* e, const pf_degradation* d, const pf_pnp_para
     if (!e->finalized) { e->err = "weights not finalized"; return PF_ERR_STATE; }
     USE_DEVICE(e);
     hipStream_t s = (hipStream_t)stream;
-    int rc = graph_stream(e, prm->use_graph, s);
-    if (rc != PF_OK) return rc;
     const int C = e->cfg.input_channels, H = e->cfg.input_height;
     if (e->cfg.output_channels != C) { e->err = "restoration needs output_channels == input_channels"; return PF_ERR_INVALID; }
-    const size_t n = (size_t)C * H * H;
-    const int Hy = deg_is_sr(d->kind) ? H / std::max(1, d->sf) : H;
-    const size_t ny = (size_t)C * Hy * Hy;
-    if (deg_is_psf(d->kind) && !psf_taps_ok(to_view(d), H, H)) { e->err = std::string("pnp_flow: ") + PSF_TAPS_RULE; return PF_ERR_INVALID; }
+    int Hy = 0;
+    int rc = check_operator(e, "pnp_flow", d, H, Hy);
+    if (rc != PF_OK) return rc;
+    if ((rc = graph_stream(e, prm->use_graph, s)) != PF_OK) return rc;
+    const size_t n = (size_t)C * H * H, ny = (size_t)C * Hy * Hy;
     if ((rc = ensure_solver(e, B, n, ny, prm->steps, prm->batch_samples ? prm->num_samples : 1)) != PF_OK) return rc;
     SolverBufs& b = *e->sb;
     Plan* plan = nullptr;
@@ -1904,7 +1896,7 @@ int pf_pnp_flow_restore(pf_engine* e, const pf_degradation* d, const pf_pnp_para
     // lazy initialisation done), the graph is captured once and kept while the captured arguments stay the same (every
     // per-batch / per-shard quantity - t, lr_t/sigma^2, noise streams, y - is read from engine-owned device buffers).
     SolverBufs::Key key; memset(&key, 0, sizeof key);
-    key = {plan, dv.kind, dv.half, dv.sf, dv.ntaps, dv.mask, dv.taps, prm->noise, prm->num_samples, prm->batch_samples, prm->noise_model, B};
+    key = {plan, dv, prm->noise, prm->num_samples, prm->batch_samples, prm->noise_model, B};
     b.graph.keep_for(e, key);
     const bool can_graph = prm->use_graph && !e->profile;
     for (int it = 0; it < prm->steps; ++it) {
@@ -1947,12 +1939,12 @@ constexpr int ODE_KRYLOV_MAX_ITER = 100;       // utils.GMRES(C_ope, d, max_iter
 
 // iterate, velocity, solve output, J^T vec, per-iteration schedule tables, cached graph(s)
 struct OdeBufs {
-    int B = 0; size_t n = 0, ny = 0; int steps = 0; int solve = 0 /* 0 closed form, 1 Fourier (circular Gaussian blur), 2 Krylov (zero-boundary blurs), 3 Fourier with the 2-D spectrum table (circular PSF), 4 Fourier on the low-resolution grid (blur, then decimate: PF_DEG_SR_FILTERED, PF_DEG_PSF_SR) */;
+    int B = 0; size_t n = 0, ny = 0; int steps = 0; DegSolve solve = DegSolve::ClosedForm;
     float *x = nullptr, *vt = nullptr, *vec = nullptr, *g = nullptr, *y = nullptr, *scratch = nullptr;
     float *dres = nullptr, *sol = nullptr, *kry = nullptr /* Krylov right-hand side, solution, workspace */; size_t kry_floats = 0;
     float *tab = nullptr /* [4][steps]: t, 1-t, r_t^2, coef */, *cur = nullptr /* [4][B] */; int* iter = nullptr;
     DevBufs mem;
-    struct Key { const void* plan; int kind, half, sf, ntaps; const void* mask; const void* taps; int B; float sigma2, delta; int pad_; };
+    struct Key { const void* plan; DegView deg; int B; float sigma2, delta; int pad_; };
     static_assert(sizeof(Key) == 3 * sizeof(void*) + 8 * sizeof(int), "OdeBufs::Key is compared with memcmp: it must have no padding bytes");
     // the step as one graph; with the Krylov solve two captured halves under one key (graph: up to d, graph2: from H_adj(sol)) with the Krylov
     // loop between them - captured together, dropped together
@@ -1961,20 +1953,19 @@ struct OdeBufs {
     void reset(pf_engine* e) { drop_graphs(e); mem.release(e); *this = OdeBufs{}; }
 };
 
-static int ensure_ode(pf_engine* e, int B, size_t n, size_t ny, int steps, int solve, int H) {
+static int ensure_ode(pf_engine* e, int B, int C, int H, int sf, size_t ny, int steps, DegSolve solve) {
     if (!e->ob) e->ob = new OdeBufs();
     OdeBufs& b = *e->ob;
+    const size_t n = (size_t)C * H * H;
     if (b.B == B && b.n == n && b.ny == ny && b.steps >= steps && b.solve == solve) return PF_OK;
     b.reset(e);
     const size_t tot = (size_t)B * n;
     int rc = PF_OK;
     auto get = [&](auto** p, size_t bytes) { if (rc == PF_OK) rc = b.mem.alloc(e, p, bytes, 4); };
     get(&b.x, tot * 4); get(&b.vt, tot * 4); get(&b.vec, tot * 4); get(&b.g, tot * 4); get(&b.y, (size_t)B * ny * 4);
-    // (solve 4: sr_solve_scratch_floats written out for a square image, sf^2 = n / ny)
-    const size_t scr = solve == 1 ? 4 * tot + 2 * (size_t)H : solve == 3 ? 4 * tot + (size_t)H * H : solve == 2 ? tot
-                     : solve == 4 ? 3 * tot + 3 * (size_t)B * ny + 1 + ny / (n / ((size_t)H * H)) + std::max((size_t)H * H, 4 * (size_t)H + 2) + (size_t)B : 0;
+    const size_t scr = deg_ode_scratch_floats(solve, B, C, H, H, sf);
     if (scr) get(&b.scratch, scr * 4);
-    if (solve == 2) {
+    if (solve == DegSolve::Krylov) {
         get(&b.dres, tot * 4); get(&b.sol, tot * 4);
         const size_t want = krylov_workspace_floats(B, n, ODE_KRYLOV_MAX_ITER) * 4;
         const hipError_t ke = rc == PF_OK ? b.mem.try_alloc(e, &b.kry, want, 4) : hipSuccess;
@@ -1988,7 +1979,7 @@ static int ensure_ode(pf_engine* e, int B, size_t n, size_t ny, int steps, int s
     }
     get(&b.tab, (size_t)4 * steps * 4); get(&b.cur, (size_t)4 * B * 4); get(&b.iter, 64);
     if (rc != PF_OK) { b.reset(e); return rc; }
-    b.kry_floats = solve == 2 ? krylov_workspace_floats(B, n, ODE_KRYLOV_MAX_ITER) : 0;
+    b.kry_floats = solve == DegSolve::Krylov ? krylov_workspace_floats(B, n, ODE_KRYLOV_MAX_ITER) : 0;
     b.B = B; b.n = n; b.ny = ny; b.steps = steps; b.solve = solve;
     return PF_OK;
 }
@@ -2002,10 +1993,9 @@ static int enqueue_ode_step(pf_engine* e, Plan* plan, const DegView& dv, const p
     const float* t_cur = b.cur; const float* omt = b.cur + B; const float* rt2 = b.cur + 2 * B; const float* coef = b.cur + 3 * B;
     int rc = run_plan(e, plan, b.x, t_cur, b.vt, s, e->solver_time_scale);                                        // v_t = v_theta(x, t), activations retained
     if (rc != PF_OK) return rc;
-    const bool sr_solve = dv.kind == DEG_PSF_SR || dv.kind == DEG_SR_FILTER;
-    hipError_t r = dv.kind == DEG_BLUR || dv.kind == DEG_PSF_BLUR || sr_solve      // (the PSF's spectrum table / the aliased spectrum was filled once, before the loop)
-        ? launch_ot_ode_vec_blur(dv, b.x, b.vt, b.y, omt, rt2, prm->sigma2, b.vec, B, C, H, H, b.scratch, s, dv.kind == DEG_PSF_BLUR || sr_solve)
-        : launch_ot_ode_vec(dv, b.x, b.vt, b.y, omt, rt2, prm->sigma2, b.vec, B, C, H, H, s);
+    hipError_t r = b.solve == DegSolve::ClosedForm      // (otherwise a Fourier family; the PSF's spectrum table / the aliased spectrum was filled once, before the loop)
+        ? launch_ot_ode_vec(dv, b.x, b.vt, b.y, omt, rt2, prm->sigma2, b.vec, B, C, H, H, s)
+        : launch_ot_ode_vec_blur(dv, b.x, b.vt, b.y, omt, rt2, prm->sigma2, b.vec, B, C, H, H, b.scratch, s, b.solve != DegSolve::FourierSeparable);
     if (r != hipSuccess) { e->err = std::string("ot_ode vec: ") + hipGetErrorString(r); return PF_ERR_HIP; }
     if ((rc = run_backward(e, plan, b.vec, b.g, s)) != PF_OK) return rc;                     // g = J^T vec
     r = launch_ot_ode_update(b.x, b.vt, b.vec, b.g, omt, coef, prm->delta, B, n, s);
@@ -2059,10 +2049,6 @@ int64_t pf_krylov_workspace_floats(int B, int C, int H, int W, int max_iter) {
 int pf_krylov_solve(const pf_degradation* d, const float* rt2_dev, float sigma2, const float* rhs, float* sol, int B, int C, int H, int W, int max_iter,
                     float tol, float atol, float* workspace, int64_t workspace_floats, int32_t* iters_out_dev, void* stream) {
     if (!d || !rt2_dev || !rhs || !sol || rhs == sol || !workspace || workspace_floats <= 0) return PF_ERR_INVALID;
-    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_PSF_SR || deg_is_sr(d->kind)) return PF_ERR_INVALID;
-    if ((d->kind == PF_DEG_GAUSSIAN_BLUR || d->kind == PF_DEG_GAUSSIAN_BLUR_ZERO) && (!d->taps || d->ntaps < 1 || d->ntaps > 127)) return PF_ERR_INVALID;
-    if (deg_is_psf(d->kind) && !psf_taps_ok(to_view(d), H, W)) return PF_ERR_INVALID;
-    if (d->kind == PF_DEG_MASK_INPAINTING && !d->mask) return PF_ERR_INVALID;
     LAUNCHCHK(launch_krylov_solve(to_view(d), rt2_dev, sigma2, rhs, sol, B, C, H, W, max_iter, tol, atol, workspace, (size_t)workspace_floats, iters_out_dev,
                                   (hipStream_t)stream));
     return PF_OK;
@@ -2076,30 +2062,23 @@ int pf_ot_ode_restore(pf_engine* e, const pf_degradation* d, const pf_ot_ode_par
     if (!e->finalized) { e->err = "weights not finalized"; return PF_ERR_STATE; }
     USE_DEVICE(e);
     hipStream_t s = (hipStream_t)stream;
-    int rc = graph_stream(e, prm->use_graph, s);
-    if (rc != PF_OK) return rc;
     const int C = e->cfg.input_channels, H = e->cfg.input_height;
     if (e->cfg.output_channels != C) { e->err = "restoration needs output_channels == input_channels"; return PF_ERR_INVALID; }
-    const size_t n = (size_t)C * H * H;
-    const bool sr_solve = d->kind == PF_DEG_SR_FILTERED || d->kind == PF_DEG_PSF_SR;      // H H^T is circulant on the low-resolution grid: one Fourier solve there
-    if (deg_is_sr(d->kind) && (d->sf <= 0 || H % d->sf)) { e->err = "ot_ode: superresolution factor must divide the image size"; return PF_ERR_INVALID; }
-    if (d->kind == PF_DEG_SR_FILTERED && (!d->taps || d->ntaps < 1 || d->ntaps > 127 || d->ntaps > H)) {
-        e->err = "ot_ode: the filtered superresolution operator needs 1 .. 127 device taps, no more than the image side"; return PF_ERR_INVALID;
-    }
-    const int Hy = deg_is_sr(d->kind) ? H / std::max(1, d->sf) : H;
-    const size_t ny = (size_t)C * Hy * Hy;
-    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_PSF_SR) { e->err = "ot_ode: unknown degradation kind"; return PF_ERR_INVALID; }
-    const bool krylov = d->kind == PF_DEG_GAUSSIAN_BLUR_ZERO || d->kind == PF_DEG_PSF_BLUR_ZERO;
-    if (d->kind == PF_DEG_GAUSSIAN_BLUR_ZERO && (!d->taps || d->ntaps < 1 || d->ntaps > 127)) { e->err = "ot_ode: the zero-boundary blur needs 1 .. 127 device taps"; return PF_ERR_INVALID; }
-    if (deg_is_psf(d->kind) && !psf_taps_ok(to_view(d), H, H)) { e->err = std::string("ot_ode: ") + PSF_TAPS_RULE; return PF_ERR_INVALID; }
-    if ((d->kind == PF_DEG_PSF_BLUR || sr_solve) && H > 2048) { e->err = "ot_ode: the Fourier solve needs H <= 2048"; return PF_ERR_INVALID; }
+    const DegView dv = to_view(d);
+    int Hy = 0;
+    int rc = check_operator(e, "ot_ode", d, H, Hy);
+    if (rc != PF_OK) return rc;
+    if (const char* broken = deg_solve_violation(dv, H, H)) { e->err = std::string("ot_ode: ") + broken; return PF_ERR_INVALID; }
+    if ((rc = graph_stream(e, prm->use_graph, s)) != PF_OK) return rc;
+    const size_t n = (size_t)C * H * H, ny = (size_t)C * Hy * Hy;
+    const DegSolve solve = deg_solve(dv.kind);
+    const bool krylov = solve == DegSolve::Krylov;
     e->ode_krylov_iters = 0;
-    if ((rc = ensure_ode(e, B, n, ny, prm->steps, krylov ? 2 : d->kind == PF_DEG_GAUSSIAN_BLUR ? 1 : d->kind == PF_DEG_PSF_BLUR ? 3 : sr_solve ? 4 : 0, H)) != PF_OK) return rc;
+    if ((rc = ensure_ode(e, B, C, H, dv.sf, ny, prm->steps, solve)) != PF_OK) return rc;
     OdeBufs& b = *e->ob;
     Plan* plan = nullptr;
     if ((rc = build_plan(e, B, true, &plan)) != PF_OK) return rc;
     e->retained_B = B; e->retained_plan = plan;
-    const DegView dv = to_view(d);
     std::vector<float> tab((size_t)4 * b.steps, 0.f);
     for (int i = 0; i < prm->steps; ++i) {
         tab[i] = prm->host_t[i]; tab[(size_t)b.steps + i] = prm->host_one_minus_t[i];
@@ -2110,15 +2089,15 @@ int pf_ot_ode_restore(pf_engine* e, const pf_degradation* d, const pf_ot_ode_par
     HIPCHK(e, hipMemcpyAsync(b.iter, &first, sizeof(int), hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(b.y, y, (size_t)B * ny * 4, hipMemcpyDeviceToDevice, s));
     HIPCHK(e, hipMemcpyAsync(b.x, x_inout, (size_t)B * n * 4, hipMemcpyDeviceToDevice, s));
-    if (dv.kind == DEG_PSF_BLUR) HIPCHK(e, launch_psf_power_spectrum(dv, H, H, b.scratch + 4 * (size_t)B * n, s));      // once per call, not per step
-    if (sr_solve) {      // the aliased spectrum, likewise (the layout of launch_ot_ode_vec_blur's scratch for these kinds)
+    if (solve == DegSolve::FourierPsf) HIPCHK(e, launch_psf_power_spectrum(dv, H, H, b.scratch + 4 * (size_t)B * n, s));      // once per call, not per step
+    if (solve == DegSolve::FourierLowRes) {      // the aliased spectrum, likewise (the layout of launch_ot_ode_vec_blur's scratch for these kinds)
         float* lam = sr_solve_lam(b.scratch, B, C, H, H, dv.sf);
         HIPCHK(e, launch_sr_aliased_spectrum(dv, H, H, lam, lam + (size_t)Hy * Hy, s));
     }
     HIPCHK(e, hipStreamSynchronize(s));      // the host tables may go away after return
 
     OdeBufs::Key key; memset(&key, 0, sizeof key);
-    key = {plan, dv.kind, dv.half, dv.sf, dv.ntaps, dv.mask, dv.taps, B, prm->sigma2, prm->delta, 0};
+    key = {plan, dv, B, prm->sigma2, prm->delta, 0};
     if (!b.graph.keep_for(e, key)) b.drop_graphs(e);
     const bool can_graph = prm->use_graph && !e->profile;
     for (int it = first; it < prm->steps; ++it) {

@@ -21,8 +21,7 @@ struct DFlowState {
     std::vector<float> host_tab;
     // cached graphs: T(z) and one closure
     struct FwdKey { const void* plan; int B, M; float delta, half_delta; int pad_; };
-    struct VgKey { const void* plan_fwd; const void* plan_ret; int kind, half, sf, ntaps; const void* mask; const void* taps; int B, M;
-                   float delta, half_delta, lmbda; int pad_; };
+    struct VgKey { const void* plan_fwd; const void* plan_ret; DegView deg; int B, M; float delta, half_delta, lmbda; int pad_; };
     static_assert(sizeof(FwdKey) == sizeof(void*) + 6 * sizeof(int), "FwdKey is compared with memcmp: it must have no padding bytes");
     static_assert(sizeof(VgKey) == 4 * sizeof(void*) + 10 * sizeof(int), "VgKey is compared with memcmp: it must have no padding bytes");
     CachedGraph fgraph, vgraph;
@@ -133,11 +132,12 @@ static int enqueue_dflow_value_and_grad(pf_engine* e, Plan* pf, Plan* pr, const 
     return PF_OK;
 }
 
-static int dflow_begin(pf_engine* e, const pf_d_flow_params* prm, bool need_graph_stream, hipStream_t& s) {
+static int dflow_begin(pf_engine* e, const pf_d_flow_params* prm, bool need_graph_stream, hipStream_t& s, const pf_degradation* d = nullptr, int* Hy = nullptr) {
     if (!e->finalized) { e->err = "weights not finalized"; return PF_ERR_STATE; }
     int rc = dflow_check_prm(e, prm);
     if (rc != PF_OK) return rc;
     if (e->cfg.output_channels != e->cfg.input_channels) { e->err = "d_flow needs output_channels == input_channels"; return PF_ERR_INVALID; }
+    if (d && (rc = check_operator(e, "d_flow", d, e->cfg.input_height, *Hy)) != PF_OK) return rc;      // the operator of the closure, before the stream is swapped
     return graph_stream(e, need_graph_stream, s);
 }
 
@@ -179,12 +179,11 @@ int pf_d_flow_value_and_grad(pf_engine* e, const pf_degradation* d, const pf_d_f
     USE_DEVICE(e);
     hipStream_t s = (hipStream_t)stream;
     const bool can_graph = prm->use_graph && !e->profile;
-    int rc = dflow_begin(e, prm, can_graph, s);
+    int Hy = 0;
+    int rc = dflow_begin(e, prm, can_graph, s, d, &Hy);
     if (rc != PF_OK) return rc;
     const int C = e->cfg.input_channels, H = e->cfg.input_height;
     const size_t n = (size_t)C * H * H;
-    int Hy = 0;
-    if ((rc = check_operator(e, "d_flow", d, H, Hy)) != PF_OK) return rc;
     const size_t ny = (size_t)C * Hy * Hy;
     if (n % 4 || ny % 4) { e->err = "d_flow: C*H*W (and the measurement's C*Hy*Wy) must be multiples of 4"; return PF_ERR_INVALID; }
     const int M = prm->steps_euler - 1;
@@ -201,8 +200,7 @@ int pf_d_flow_value_and_grad(pf_engine* e, const pf_degradation* d, const pf_d_f
     const DegView dv = to_view(d);
     if (can_graph) {
         DFlowState::VgKey key; memset(&key, 0, sizeof key);
-        key.plan_fwd = pf; key.plan_ret = pr; key.kind = dv.kind; key.half = dv.half; key.sf = dv.sf; key.ntaps = dv.ntaps; key.mask = dv.mask;
-        key.taps = dv.taps; key.B = B; key.M = M; key.delta = prm->delta; key.half_delta = prm->half_delta; key.lmbda = lmbda;
+        key.plan_fwd = pf; key.plan_ret = pr; key.deg = dv; key.B = B; key.M = M; key.delta = prm->delta; key.half_delta = prm->half_delta; key.lmbda = lmbda;
         if (!st->vgraph.keep_for(e, key) &&
             (rc = st->vgraph.capture(e, s, key, {pf, pr}, [&] { return enqueue_dflow_value_and_grad(e, pf, pr, dv, prm, lmbda, s); })) != PF_OK) return rc;
         if ((rc = st->vgraph.launch(e, s)) != PF_OK) return rc;

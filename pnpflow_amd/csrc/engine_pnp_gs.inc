@@ -20,7 +20,7 @@ struct PnpGsState {
     int* iter = nullptr;
     double* dbl = nullptr;                                 // [0] alpha, [1] |H(x) - y|^2 carried, [2] g, [8 ..) 3 x PNPGS_MAX_PARTS partials, then [max_iter][2] (gap, threshold)
     DevBufs mem;
-    struct Key { const void* plan; int kind, half, sf, ntaps; const void* mask; const void* taps; int B, algo, noise_model, skip, max_iter; float grad_coef; };
+    struct Key { const void* plan; DegView deg; int B, algo, noise_model, skip, max_iter; float grad_coef; };
     static_assert(sizeof(Key) == 3 * sizeof(void*) + 10 * sizeof(int), "PnpGsState::Key is compared with memcmp: it must have no padding bytes");
     CachedGraph graph;
     void reset(pf_engine* e) { graph.drop(e); /* its nodes point into the buffers */ mem.release(e); *this = PnpGsState{}; }
@@ -152,19 +152,11 @@ int pf_pnp_gs_restore(pf_engine* e, const pf_degradation* d, const pf_pnp_gs_par
     }
     if (!prm->host_sigma_den) { e->err = "pnp_gs: host_sigma_den (the denoiser level of every iteration) is required"; return PF_ERR_INVALID; }
     if (!(prm->alpha > 0.0)) { e->err = "pnp_gs: alpha must be positive"; return PF_ERR_INVALID; }
-    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_PSF_SR) { e->err = "pnp_gs: unknown degradation kind"; return PF_ERR_INVALID; }
     const int C = e->cfg.input_channels, H = e->cfg.input_height;
-    const bool sr = deg_is_sr(d->kind);
-    if (sr && (d->sf <= 0 || H % d->sf)) { e->err = "pnp_gs: superresolution factor must divide the image size"; return PF_ERR_INVALID; }
-    if ((d->kind == PF_DEG_GAUSSIAN_BLUR || d->kind == PF_DEG_SR_FILTERED) && (!d->taps || d->ntaps < 1 || d->ntaps > 127 || d->ntaps > H)) {
-        e->err = "pnp_gs: the filtered operators need 1..127 device taps (at most the image size)"; return PF_ERR_INVALID;
-    }
-    if (d->kind == PF_DEG_GAUSSIAN_BLUR_ZERO && (!d->taps || d->ntaps < 1 || d->ntaps > 127)) {
-        e->err = "pnp_gs: the zero-boundary blur needs 1..127 device taps"; return PF_ERR_INVALID;
-    }
-    if (deg_is_psf(d->kind) && !psf_taps_ok(to_view(d), H, H)) { e->err = std::string("pnp_gs: ") + PSF_TAPS_RULE; return PF_ERR_INVALID; }
-    if (d->kind == PF_DEG_MASK_INPAINTING && !d->mask) { e->err = "pnp_gs: mask inpainting needs a device mask"; return PF_ERR_INVALID; }
-    const int Hy = sr ? H / d->sf : H;
+    int Hy = 0;
+    int rc = check_operator(e, "pnp_gs", d, H, Hy);
+    if (rc != PF_OK) return rc;
+    if ((d->kind == PF_DEG_GAUSSIAN_BLUR || d->kind == PF_DEG_SR_FILTERED) && d->ntaps > H) { e->err = "pnp_gs: the circular filtered operators need at most as many taps as the image side"; return PF_ERR_INVALID; }
     const size_t n = (size_t)C * H * H, ny = (size_t)C * Hy * Hy;
     if (n % 4 || ny % 4) { e->err = "pnp_gs: C*H*W (and the measurement's C*Hy*Wy) must be multiples of 4"; return PF_ERR_INVALID; }
     if (prm->algo == 1 && (H * H) % 4) { e->err = "pnp_gs: algo 1 needs H*W to be a multiple of 4"; return PF_ERR_INVALID; }
@@ -172,13 +164,12 @@ int pf_pnp_gs_restore(pf_engine* e, const pf_degradation* d, const pf_pnp_gs_par
     USE_DEVICE(e);
     hipStream_t s = (hipStream_t)stream;
     const bool can_graph = prm->use_graph && !e->profile;
-    int rc = graph_stream(e, can_graph, s);
-    if (rc != PF_OK) return rc;
+    if ((rc = graph_stream(e, can_graph, s)) != PF_OK) return rc;
     if ((rc = ensure_pnpgs(e, B, n, ny, prm->max_iter)) != PF_OK) return rc;
     PnpGsState* st = e->pnpgs;
     if (prm->algo == 2 && d->kind == PF_DEG_PSF_BLUR && !st->pw2 && (rc = st->mem.alloc4(e, &st->pw2, (size_t)H * H)) != PF_OK) return rc;
     if (prm->algo == 3 && !st->srs) {      // (ensure_pnpgs resets the state, and these with it, when B, n or ny change)
-        if ((rc = st->mem.alloc4(e, &st->srs, 3 * (size_t)B * n + 3 * (size_t)B * ny + 1 + (size_t)B + std::max((size_t)H * H, 4 * (size_t)H + 2))) != PF_OK) return rc;
+        if ((rc = st->mem.alloc4(e, &st->srs, sr_solve_scratch_floats(B, C, H, H, d->sf) - (size_t)Hy * Hy)) != PF_OK) return rc;      // (lam has a buffer of its own)
         if ((rc = st->mem.alloc4(e, &st->lam, (size_t)Hy * Hy)) != PF_OK) return rc;
     }
     Plan* pr = nullptr;
@@ -207,12 +198,12 @@ int pf_pnp_gs_restore(pf_engine* e, const pf_degradation* d, const pf_pnp_gs_par
     if (prm->algo == 3) {
         // once per call: H_adj(noisy) and the aliased spectrum (its source table goes into the tail of the prox scratch)
         GS_LAUNCH("H_adj", launch_deg_Hadj(dv, st->y, st->hadj, B, C, H, H, st->scr, s));
-        GS_LAUNCH("aliased spectrum", launch_sr_aliased_spectrum(dv, H, H, st->lam, st->srs + 3 * tot + 3 * toty + 1 + (size_t)B, s));
+        GS_LAUNCH("aliased spectrum", launch_sr_aliased_spectrum(dv, H, H, st->lam, st->srs + sr_prox_scratch_floats(B, C, H, H, dv.sf), s));
     }
     HIPCHK(e, hipStreamSynchronize(s));      // the host table may go away after return
 
     PnpGsState::Key key; memset(&key, 0, sizeof key);
-    key.plan = pr; key.kind = dv.kind; key.half = dv.half; key.sf = dv.sf; key.ntaps = dv.ntaps; key.mask = dv.mask; key.taps = dv.taps; key.B = B;
+    key.plan = pr; key.deg = dv; key.B = B;
     key.algo = prm->algo; key.noise_model = prm->noise_model; key.skip = prm->skip_grad_step ? 1 : 0; key.max_iter = st->max_iter; key.grad_coef = prm->grad_coef;
     st->graph.keep_for(e, key);
     for (int it = first; it < prm->stop; ++it) {

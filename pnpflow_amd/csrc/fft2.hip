@@ -272,9 +272,7 @@ hipError_t fourier_solve(const float* y, const float* hx, float2* z, const float
     return hipGetLastError();
 }
 
-// The scratch of the blur-then-decimate solves (sr_solve_scratch_floats), S = B C H W, Sl = S / sf^2:
-//   [S] x1_hat | [2 S] the operator's own scratch | [Sl] H(.), then sol | (up to the next 8-byte boundary) [2 Sl] complex plane | [Hl Wl] lam, or the prox's B
-//   coefficients | the spectrum's source (launch_sr_aliased_spectrum's tmp)
+// The scratch of the blur-then-decimate solves (its size and layout: sr_solve_scratch_floats, deg_rules.h), S = B C H W, Sl = S / sf^2
 struct SrScratch {
     float *buf0, *opscr, *hx, *lam; float2* z;
     SrScratch(float* scratch, size_t S, size_t Sl) {
@@ -284,19 +282,7 @@ struct SrScratch {
     }
 };
 
-bool sr_solve_shape_ok(const DegView& d, int H, int W) {
-    if (d.kind == DEG_PSF_SR) return psf_taps_ok(d, H, W) && H <= 2048 && W <= 2048;
-    return d.kind == DEG_SR_FILTER && d.taps && d.ntaps >= 1 && d.ntaps <= 127 && d.ntaps <= H && d.ntaps <= W && d.sf >= 1 && H % d.sf == 0 && W % d.sf == 0 &&
-           H <= 2048 && W <= 2048;
-}
-
 }  // namespace
-
-size_t sr_solve_scratch_floats(int B, int C, int H, int W, int sf) {
-    if (sf < 1) sf = 1;
-    const size_t S = (size_t)B * C * H * W, Sl = S / ((size_t)sf * sf);
-    return 3 * S + 3 * Sl + 1 + (size_t)(H / sf) * (W / sf) + std::max((size_t)H * W, 2 * ((size_t)H + W) + 2) + (size_t)B;      // (+ 1: the alignment gap)
-}
 
 float* sr_solve_lam(float* scratch, int B, int C, int H, int W, int sf) {
     const size_t S = (size_t)B * C * H * W;
@@ -367,10 +353,10 @@ hipError_t launch_fft_prox_sr(const DegView& d, const float* in, const double* a
 // scratch: 4*B*C*H*W + H + W floats; DEG_PSF_BLUR: 4*B*C*H*W + H*W (the 2-D spectrum table, filled here unless spectrum_ready)
 hipError_t launch_ot_ode_vec_blur(const DegView& d, const float* x, const float* vt, const float* y, const float* one_minus_t,
                                   const float* rt2, float sigma2, float* vec, int B, int C, int H, int W, float* scratch, hipStream_t s, bool spectrum_ready) {
-    if (d.kind == DEG_PSF_SR || d.kind == DEG_SR_FILTER)
-        return scratch ? ot_ode_vec_sr(d, x, vt, y, one_minus_t, rt2, sigma2, vec, B, C, H, W, scratch, s, spectrum_ready) : hipErrorInvalidValue;
-    const bool psf = d.kind == DEG_PSF_BLUR;
-    if (!scratch || (d.kind != DEG_BLUR && !psf) || H > 2048 || W > 2048 || d.ntaps > H || d.ntaps > W) return hipErrorInvalidValue;
+    const DegSolve solve = deg_solve(d.kind);
+    if (!scratch || solve == DegSolve::ClosedForm || solve == DegSolve::Krylov || deg_solve_violation(d, H, W)) return hipErrorInvalidValue;
+    if (solve == DegSolve::FourierLowRes) return ot_ode_vec_sr(d, x, vt, y, one_minus_t, rt2, sigma2, vec, B, C, H, W, scratch, s, spectrum_ready);
+    const bool psf = solve == DegSolve::FourierPsf;
     const size_t S = (size_t)B * C * H * W;
     float* buf0 = scratch; float* buf1 = scratch + S; float2* z = reinterpret_cast<float2*>(scratch + 2 * S);
     float* pw_h = scratch + 4 * S; float* pw_w = pw_h + H;
@@ -397,7 +383,7 @@ hipError_t launch_psf_power_spectrum(const DegView& d, int H, int W, float* pw2,
 }
 
 hipError_t launch_blur_power_spectrum(const DegView& d, int H, int W, float* pw_h, float* pw_w, hipStream_t s) {
-    if (d.kind != DEG_BLUR || !d.taps || H > 2048 || W > 2048 || d.ntaps > H || d.ntaps > W) return hipErrorInvalidValue;
+    if (deg_solve(d.kind) != DegSolve::FourierSeparable || deg_solve_violation(d, H, W)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(blur_power_spectrum_kernel, dim3((H + 63) / 64), dim3(64), 0, s, d.taps, d.ntaps, H, pw_h);
     hipLaunchKernelGGL(blur_power_spectrum_kernel, dim3((W + 63) / 64), dim3(64), 0, s, d.taps, d.ntaps, W, pw_w);
     return hipGetLastError();

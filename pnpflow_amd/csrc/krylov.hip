@@ -334,7 +334,7 @@ hipError_t launch_krylov_solve(const DegView& d, const float* rt2, float sigma2,
                                float tol, float atol, float* ws, size_t ws_floats, int* iters_out, hipStream_t s, int* iterations_run) {
     if (iterations_run) *iterations_run = 0;
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || max_iter < 0 || max_iter > KR_MAXM || !rt2 || !rhs || !sol || !ws) return hipErrorInvalidValue;
-    if (deg_is_sr(d.kind)) return hipErrorInvalidValue;       // the measurement must have the image's shape
+    if (deg_rule_violation(d, H, W) || deg_is_sr(d.kind)) return hipErrorInvalidValue;       // the measurement must have the image's shape
     if ((size_t)C * H * W > (size_t)0x7fffffff - KR_CHUNK) return hipErrorInvalidValue;
     const size_t n = (size_t)C * H * W;
     KrylovState k{};

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <atomic>
 
+#include "deg_rules.h"
+
 namespace pf {
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE attribute of a kernel: a process may hold engines on several devices
@@ -240,26 +242,11 @@ hipError_t launch_softmax_bwd(const float* A, float* dA, int64_t rows, int cols,
 hipError_t launch_sumpool2(const float* in, float* out, int B, int H, int W, int C, int accumulate, hipStream_t s);
 
 // pointwise / operator kernels (NCHW fp32 images)
-enum { DEG_DENOISE = 0, DEG_BOX = 1, DEG_MASK = 2, DEG_SR = 3, DEG_BLUR = 4, DEG_SR_FILTER = 5, DEG_BLUR_ZERO = 6 /* same taps, samples outside the image are 0 */,
-       DEG_PSF_BLUR = 7 /* circular blur with a square 2-D point-spread function: ntaps = its side K (odd, <= PSF_MAX_SIDE), taps = [K][K] */,
-       DEG_PSF_BLUR_ZERO = 8 /* the same taps, samples outside the image are 0 */,
-       DEG_PSF_SR = 9 /* the circular blur of DEG_PSF_BLUR sampled at (i sf, j sf): y = (k (*) x) decimated by sf (1 .. PSF_SR_MAX_SF, dividing H and W) */ };
-constexpr int PSF_MAX_SIDE = 63;
-constexpr int PSF_SR_MAX_SF = 8;
-inline bool deg_is_psf(int kind) { return kind == DEG_PSF_BLUR || kind == DEG_PSF_BLUR_ZERO || kind == DEG_PSF_SR; }      // the kinds with [K][K] taps (psf_taps_ok)
-inline bool deg_is_sr(int kind) { return kind == DEG_SR || kind == DEG_SR_FILTER || kind == DEG_PSF_SR; }                   // the measurement is [H / sf][W / sf]
-struct DegView {       // device-side view of pf_degradation
-    int kind, half, sf, ntaps;
-    const uint8_t* mask;
-    const float* taps;
-};
+// (the DEG_* kinds, DegView and the rules of an operator: deg_rules.h)
 hipError_t launch_deg_H(const DegView& d, const float* x, float* y, int B, int C, int H, int W, float* scratch, hipStream_t s);
 hipError_t launch_deg_Hadj(const DegView& d, const float* y, float* x, int B, int C, int H, int W, float* scratch, hipStream_t s);
 hipError_t launch_grad_step(const DegView& d, const float* x, const float* y, const float* coef, float* z,
                             int B, int C, int H, int W, float* scratch, int laplace, hipStream_t s);
-// the 2-D point-spread-function kinds (psf.hip): K odd, 1 .. PSF_MAX_SIDE, device taps, and K <= min(H, W) for the circular kinds; DEG_PSF_SR also
-// needs sf in 1 .. PSF_SR_MAX_SF dividing H and W
-bool psf_taps_ok(const DegView& d, int H, int W);
 // DEG_PSF_SR, one application in one launch, no scratch: sign +1 = H ([H][W] -> [H / sf][W / sf]), -1 = H_adj (the polyphase form: no zero-filled tensor);
 // mode / aux / coef as launch_psf2d, on the output's grid; in == out is refused
 hipError_t launch_psf_sr(const DegView& d, const float* in, float* out, int B, int C, int H, int W, int sign, int mode, const float* aux, const float* coef,
@@ -299,7 +286,6 @@ hipError_t launch_ot_ode_vec_blur(const DegView& d, const float* x, const float*
                                   bool spectrum_ready = false);
 // DEG_PSF_SR / DEG_SR_FILTER (blur, then decimate by sf): launch_ot_ode_vec_blur takes them with scratch of sr_solve_scratch_floats(B, C, H, W, sf) floats;
 // spectrum_ready: the caller has filled lam = sr_solve_lam(scratch, ...) with launch_sr_aliased_spectrum(d, H, W, lam, lam + (H / sf) * (W / sf), s)
-size_t sr_solve_scratch_floats(int B, int C, int H, int W, int sf);
 float* sr_solve_lam(float* scratch, int B, int C, int H, int W, int sf);
 // lam[H / sf][W / sf] <- the eigenvalues of H H^T, 1 / sf^2 sum_{a, b < sf} |fft2 filter|^2 [u + a H / sf][v + b W / sf]; tmp: H*W floats (DEG_PSF_SR) or 2 (H + W) + 2 (DEG_SR_FILTER)
 hipError_t launch_sr_aliased_spectrum(const DegView& d, int H, int W, float* lam, float* tmp, hipStream_t s);

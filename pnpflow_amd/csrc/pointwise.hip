@@ -382,26 +382,24 @@ static hipError_t blur2(const DegView& d, const float* in, float* tmp, float* ou
 }
 
 hipError_t launch_deg_H(const DegView& d, const float* x, float* y, int B, int C, int H, int W, float* scratch, hipStream_t s) {
+    if (deg_rule_violation(d, H, W) || (deg_is_separable(d.kind) && !scratch)) return hipErrorInvalidValue;
     switch (d.kind) {
         case DEG_DENOISE: case DEG_BOX: case DEG_MASK:
             if (W % 4 == 0 && aligned16(x, y) && ((uintptr_t)d.mask & 3) == 0) hipLaunchKernelGGL(mask_apply4_kernel, grid_for(C * H * W / 4, B), dim3(256), 0, s, d, (const float4*)x, (float4*)y, C * H * W / 4, H, W / 4);
             else hipLaunchKernelGGL(mask_apply_kernel, grid_for(C * H * W, B), dim3(256), 0, s, d, x, y, C, H, W);
             return hipGetLastError();
         case DEG_SR: {
-            if (d.sf <= 0 || H % d.sf || W % d.sf) return hipErrorInvalidValue;
             const size_t n = (size_t)B * C * (H / d.sf) * (W / d.sf);
             hipLaunchKernelGGL(decimate_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65535)), dim3(256), 0, s, x, y, B * C, H, W, d.sf);
             return hipGetLastError();
         }
         case DEG_BLUR: case DEG_BLUR_ZERO:
-            if (!scratch || !d.taps || d.ntaps < 1 || d.ntaps > 127) return hipErrorInvalidValue;
             return blur2(d, x, scratch, y, B, C, H, W, +1, 0, nullptr, nullptr, s);
         case DEG_PSF_BLUR: case DEG_PSF_BLUR_ZERO:      // one launch, no scratch (psf.hip)
             return launch_psf2d(d, x, y, B, C, H, W, +1, 0, nullptr, nullptr, s);
         case DEG_PSF_SR:           // blur and decimate in one launch: K^2 multiply-adds per low-resolution output (psf.hip)
             return launch_psf_sr(d, x, y, B, C, H, W, +1, 0, nullptr, nullptr, s);
         case DEG_SR_FILTER: {      // y = decimate(filter (*) x)
-            if (!scratch || d.ntaps < 1 || d.ntaps > 127 || d.sf <= 0 || H % d.sf || W % d.sf) return hipErrorInvalidValue;
             float* s0 = scratch; float* s1 = scratch + (size_t)B * C * H * W;
             hipError_t e = blur2(d, x, s0, s1, B, C, H, W, +1, 0, nullptr, nullptr, s);
             if (e != hipSuccess) return e;
@@ -414,26 +412,24 @@ hipError_t launch_deg_H(const DegView& d, const float* x, float* y, int B, int C
 }
 
 hipError_t launch_deg_Hadj(const DegView& d, const float* y, float* x, int B, int C, int H, int W, float* scratch, hipStream_t s) {
+    if (deg_rule_violation(d, H, W) || (deg_is_separable(d.kind) && !scratch)) return hipErrorInvalidValue;
     switch (d.kind) {
         case DEG_DENOISE: case DEG_BOX: case DEG_MASK:
             if (W % 4 == 0 && aligned16(x, y) && ((uintptr_t)d.mask & 3) == 0) hipLaunchKernelGGL(mask_apply4_kernel, grid_for(C * H * W / 4, B), dim3(256), 0, s, d, (const float4*)y, (float4*)x, C * H * W / 4, H, W / 4);
             else hipLaunchKernelGGL(mask_apply_kernel, grid_for(C * H * W, B), dim3(256), 0, s, d, y, x, C, H, W);
             return hipGetLastError();
         case DEG_SR: {
-            if (d.sf <= 0 || H % d.sf || W % d.sf) return hipErrorInvalidValue;
             const size_t n = (size_t)B * C * H * W;
             hipLaunchKernelGGL(zerofill_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65535)), dim3(256), 0, s, y, x, B * C, H, W, d.sf);
             return hipGetLastError();
         }
         case DEG_BLUR: case DEG_BLUR_ZERO:
-            if (!scratch || !d.taps || d.ntaps < 1 || d.ntaps > 127) return hipErrorInvalidValue;
             return blur2(d, y, scratch, x, B, C, H, W, -1, 0, nullptr, nullptr, s);
         case DEG_PSF_BLUR: case DEG_PSF_BLUR_ZERO:
             return launch_psf2d(d, y, x, B, C, H, W, -1, 0, nullptr, nullptr, s);
         case DEG_PSF_SR:           // the polyphase adjoint: no zero-filled tensor
             return launch_psf_sr(d, y, x, B, C, H, W, -1, 0, nullptr, nullptr, s);
         case DEG_SR_FILTER: {      // x = filter^T (*) zerofill(y)
-            if (!scratch || d.ntaps < 1 || d.ntaps > 127 || d.sf <= 0 || H % d.sf || W % d.sf) return hipErrorInvalidValue;
             float* s0 = scratch; float* s1 = scratch + (size_t)B * C * H * W;
             const size_t n = (size_t)B * C * H * W;
             hipLaunchKernelGGL(zerofill_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65535)), dim3(256), 0, s, y, s0, B * C, H, W, d.sf);
@@ -497,6 +493,7 @@ __global__ __launch_bounds__(256) void sr_residual_kernel(const float* hx, const
 
 hipError_t launch_grad_step(const DegView& d, const float* x, const float* y, const float* coef, float* z,
                             int B, int C, int H, int W, float* scratch, int laplace, hipStream_t s) {
+    if (deg_rule_violation(d, H, W) || ((deg_is_separable(d.kind) || deg_is_psf(d.kind)) && !scratch)) return hipErrorInvalidValue;
     dim3 g = grid_for(C * H * W, B);
     switch (d.kind) {
         case DEG_DENOISE: case DEG_BOX: case DEG_MASK:
@@ -506,14 +503,12 @@ hipError_t launch_grad_step(const DegView& d, const float* x, const float* y, co
             else hipLaunchKernelGGL(grad_step_mask_kernel, g, dim3(256), 0, s, d, x, y, coef, z, C, H, W, laplace);
             return hipGetLastError();
         case DEG_SR:
-            if (d.sf <= 0 || H % d.sf || W % d.sf) return hipErrorInvalidValue;
             if (W % 4 == 0 && aligned16(x, z))
                 hipLaunchKernelGGL(grad_step_sr4_kernel, grid_for(C * H * W / 4, B), dim3(256), 0, s, (const float4*)x, y, coef, (float4*)z, C * H * W / 4, C, H, W / 4,
                                    d.sf, laplace);
             else hipLaunchKernelGGL(grad_step_sr_kernel, g, dim3(256), 0, s, x, y, coef, z, C, H, W, d.sf, laplace);
             return hipGetLastError();
         case DEG_BLUR: case DEG_BLUR_ZERO: {
-            if (!scratch || !d.taps || d.ntaps < 1 || d.ntaps > 127) return hipErrorInvalidValue;
             float* s0 = scratch;
             float* s1 = scratch + (size_t)B * C * H * W;
             hipError_t e = blur2(d, x, s0, s1, B, C, H, W, +1, laplace ? 3 : 1, y, nullptr, s);     // s1 = Hx - y  (or its sign)
@@ -521,19 +516,16 @@ hipError_t launch_grad_step(const DegView& d, const float* x, const float* y, co
             return blur2(d, s1, s0, z, B, C, H, W, -1, 2, x, coef, s);                 // z = x - coef*H_adj(s1)
         }
         case DEG_PSF_BLUR: case DEG_PSF_BLUR_ZERO: {      // the same two applications; scratch: B*C*H*W floats (the residual)
-            if (!scratch || !psf_taps_ok(d, H, W)) return hipErrorInvalidValue;
             hipError_t e = launch_psf2d(d, x, scratch, B, C, H, W, +1, laplace ? 3 : 1, y, nullptr, s);      // scratch = Hx - y  (or its sign)
             if (e != hipSuccess) return e;
             return launch_psf2d(d, scratch, z, B, C, H, W, -1, 2, x, coef, s);                              // z = x - coef*H_adj(scratch)
         }
         case DEG_PSF_SR: {         // two applications; scratch: B*C*H*W / sf^2 floats (the low-resolution residual)
-            if (!scratch || !psf_taps_ok(d, H, W)) return hipErrorInvalidValue;
             hipError_t e = launch_psf_sr(d, x, scratch, B, C, H, W, +1, laplace ? 3 : 1, y, nullptr, s);    // scratch = Hx - y  (or its sign)
             if (e != hipSuccess) return e;
             return launch_psf_sr(d, scratch, z, B, C, H, W, -1, 2, x, coef, s);                             // z = x - coef*H_adj(scratch)
         }
         case DEG_SR_FILTER: {
-            if (!scratch || d.ntaps < 1 || d.ntaps > 127 || d.sf <= 0 || H % d.sf || W % d.sf) return hipErrorInvalidValue;
             float* s0 = scratch;
             float* s1 = scratch + (size_t)B * C * H * W;
             hipError_t e = blur2(d, x, s0, s1, B, C, H, W, +1, 0, nullptr, nullptr, s);             // s1 = filter (*) x
@@ -780,10 +772,8 @@ __global__ __launch_bounds__(256) void ot_ode_vec_kernel(DegView d, const float*
 
 hipError_t launch_ot_ode_vec(const DegView& d, const float* x, const float* vt, const float* y, const float* one_minus_t, const float* rt2,
                              float sigma2, float* vec, int B, int C, int H, int W, hipStream_t s) {
-    if (d.kind == DEG_BLUR) return hipErrorInvalidValue;   // Fourier-domain solve: launch_ot_ode_vec_blur (fft2.hip)
-    if (d.kind == DEG_BLUR_ZERO) return hipErrorInvalidValue;   // no closed form: launch_krylov_solve (krylov.hip)
-    if (deg_is_psf(d.kind)) return hipErrorInvalidValue;        // DEG_PSF_BLUR, DEG_PSF_SR: launch_ot_ode_vec_blur; DEG_PSF_BLUR_ZERO: launch_krylov_solve
-    if (d.kind == DEG_SR && (d.sf <= 0 || H % d.sf || W % d.sf)) return hipErrorInvalidValue;
+    // the Fourier families: launch_ot_ode_vec_blur (fft2.hip); no closed form: launch_krylov_solve (krylov.hip)
+    if (deg_solve(d.kind) != DegSolve::ClosedForm || deg_rule_violation(d, H, W)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(ot_ode_vec_kernel, grid_for(C * H * W, B), dim3(256), 0, s, d, x, vt, y, one_minus_t, rt2, sigma2, vec, C, H, W);
     return hipGetLastError();
 }

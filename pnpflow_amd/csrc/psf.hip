@@ -247,12 +247,6 @@ __global__ __launch_bounds__(256) void psf_sr_adj_kernel(const float* __restrict
     }
 }
 
-bool psf_taps_ok(const DegView& d, int H, int W) {
-    if (!d.taps || d.ntaps < 1 || d.ntaps > PSF_MAX_SIDE || !(d.ntaps & 1)) return false;
-    if (d.kind == DEG_PSF_SR) return d.sf >= 1 && d.sf <= PSF_SR_MAX_SF && H % d.sf == 0 && W % d.sf == 0 && d.ntaps <= std::min(H, W);
-    return d.kind == DEG_PSF_BLUR_ZERO || (d.kind == DEG_PSF_BLUR && d.ntaps <= std::min(H, W));      // the circular filter must hold the kernel
-}
-
 // rows of low-resolution outputs per workgroup of psf_sr_fwd_kernel and the LDS they need: 64 rows (one per thread row) while the staged neighbourhood
 // fits 64 KB; a large sf x K product takes up to 160 KB before the tile drops under 16 rows
 static size_t psf_sr_fwd_lds(int K, int sf, int TLY) {

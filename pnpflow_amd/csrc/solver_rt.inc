@@ -95,18 +95,12 @@ static int graph_stream(pf_engine* e, bool need, hipStream_t& s) {
     return PF_OK;
 }
 
-// the operator rules D-Flow and Flow-Priors share (`who`: the prefix of their messages); Hy: the side of the measurement
+// the operator rules (deg_rules.h) every solver applies to its H x H images before it allocates, copies or launches anything (`who`: the prefix of the
+// message); Hy: the side of the measurement
 static int check_operator(pf_engine* e, const char* who, const pf_degradation* d, int H, int& Hy) {
-    const std::string p = std::string(who) + ": ";
-    if (d->kind < PF_DEG_DENOISING || d->kind > PF_DEG_PSF_SR) { e->err = p + "unknown degradation kind"; return PF_ERR_INVALID; }
-    const bool sr = deg_is_sr(d->kind);
-    if (sr && (d->sf <= 0 || H % d->sf)) { e->err = p + "superresolution factor must divide the image size"; return PF_ERR_INVALID; }
-    if ((d->kind == PF_DEG_GAUSSIAN_BLUR || d->kind == PF_DEG_GAUSSIAN_BLUR_ZERO || d->kind == PF_DEG_SR_FILTERED) && (!d->taps || d->ntaps < 1 || d->ntaps > 127)) {
-        e->err = p + "the filtered operators need 1..127 device taps"; return PF_ERR_INVALID;
-    }
-    if (deg_is_psf(d->kind) && !psf_taps_ok(to_view(d), H, H)) { e->err = p + PSF_TAPS_RULE; return PF_ERR_INVALID; }
-    if (d->kind == PF_DEG_MASK_INPAINTING && !d->mask) { e->err = p + "mask inpainting needs a device mask"; return PF_ERR_INVALID; }
-    Hy = sr ? H / d->sf : H;
+    const DegView dv = to_view(d);
+    if (const char* broken = deg_rule_violation(dv, H, H)) { e->err = std::string(who) + ": " + broken; return PF_ERR_INVALID; }
+    Hy = deg_out_side(dv, H);
     return PF_OK;
 }
 

@@ -268,7 +268,7 @@ def test_abi_declares_the_kinds_and_the_spectrum_entry_point():
     assert (L.PF_ABI_VERSION, L.PF_DEG_PSF_BLUR, L.PF_DEG_PSF_BLUR_ZERO, L.PSF_MAX_SIDE) == (6, 7, 8, 63)
     assert re.search(r"\bpf_psf_power_spectrum\s*\(", hdr) and "pf_psf_power_spectrum" in L.SIGNATURES
     assert [f[0] for f in L.PfDegradation._fields_] == ["kind", "half_size_mask", "sf", "ntaps", "mask", "taps"]
-    common = open(os.path.join(ROOT, "pnpflow_amd", "csrc", "pf_common.h")).read()
+    common = open(os.path.join(ROOT, "pnpflow_amd", "csrc", "deg_rules.h")).read()
     assert re.search(r"DEG_PSF_BLUR\s*=\s*7\b", common) and re.search(r"DEG_PSF_BLUR_ZERO\s*=\s*8\b", common)
     assert "psf.hip" in G.SOURCES
     lib = L.load()

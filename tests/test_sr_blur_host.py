@@ -199,7 +199,7 @@ def test_abi_declares_kind_9_additively():
     assert [f[0] for f in L.PfDegradation._fields_] == ["kind", "half_size_mask", "sf", "ntaps", "mask", "taps"]
     for name in ("pf_sr_aliased_spectrum", "pf_sr_solve_scratch_floats", "pf_sr_prox"):
         assert re.search(r"\b" + name + r"\s*\(", hdr) and name in L.SIGNATURES
-    common = open(os.path.join(ROOT, "pnpflow_amd", "csrc", "pf_common.h")).read()
+    common = open(os.path.join(ROOT, "pnpflow_amd", "csrc", "deg_rules.h")).read()
     assert re.search(r"DEG_PSF_SR\s*=\s*9\b", common) and re.search(r"PSF_SR_MAX_SF\s*=\s*8\b", common)
     lib = L.load()
     assert lib.pf_abi_version() == 6 and hasattr(lib, "pf_sr_prox")
