@@ -237,10 +237,13 @@ __global__ __launch_bounds__(256) void krylov_normalise_kernel(const float* __re
     store4<VEC>(dst + (size_t)b * n, e, n, v);
 }
 
-// w = rt2[b] * hh + sigma2 * v, each product rounded before the sum (ot_ode.py:124); w may be hh
+// w = rt2[b] * hh + sigma2 * v, each product rounded before the sum (ot_ode.py:124); w may be hh.  Contraction is switched off in the body:
+// __fadd_rn(__fmul_rn(..), __fmul_rn(..)) inlines to a plain * and + that the compiler fused into mul + fma - in every lane of the float4
+// instantiation and in two of the scalar one's four, so the two disagreed in the last bit and neither rounded as torch does.
 template <bool VEC>
 __global__ __launch_bounds__(256) void krylov_operator_kernel(const float* __restrict__ hh, const float* __restrict__ v, float* __restrict__ w, int n,
                                                              const float* __restrict__ rt2, float sigma2, const int* __restrict__ done) {
+#pragma clang fp contract(off)
     const int b = blockIdx.y;
     if (done[b]) return;
     const float r2 = rt2[b];
@@ -250,7 +253,10 @@ __global__ __launch_bounds__(256) void krylov_operator_kernel(const float* __res
     load4<VEC>(hh + (size_t)b * n, e, n, a);
     load4<VEC>(v + (size_t)b * n, e, n, c);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) a[j] = __fadd_rn(__fmul_rn(r2, a[j]), __fmul_rn(sigma2, c[j]));
+    for (int j = 0; j < 4; ++j) {
+        const float p0 = r2 * a[j], p1 = sigma2 * c[j];
+        a[j] = p0 + p1;
+    }
     store4<VEC>(w + (size_t)b * n, e, n, a);
 }
 

@@ -1,10 +1,13 @@
 """Fixtures of the zero-boundary Gaussian blur (GaussianDeblurring with mode != "fft") from the REAL reference on the CPU.
 
-Run in the build container only:   python tools/make_golden_spatial.py [op] [gmres] [pnp] [ot_ode]
+Run in the build container only:   python tools/make_golden_spatial.py [op] [gmres] [gmres_paths] [pnp] [ot_ode]
 Writes data only, under tests/golden/:
   zero_blur_op.npz        H (= H_adj) of det_image at 2 x 3 x 64 x 64 for blur sigma 1 and 3, K = 61
   zero_blur_gmres.npz     utils.GMRES on r_t^2 H H^T + sigma^2 I (cases of tests/zero_blur_restatement.py: max_iter 100 and 5), its iteration
                           counts, and the measured distance between that fp32 result and the fp64 restatement
+  krylov_paths.npz        (target gmres_paths, only when named) utils.GMRES in fp32 on every case of tests/krylov_reference.py: its Krylov vector
+                          counts and zero_blur_restatement.gmres64's, per image max|ref32 - exact fp64 solution| (capped cases: - gmres64's iterate
+                          at the cap) and max|exact|.  Scalars and small integer arrays only; the right-hand sides are regenerated from seeds
   pnp_traj_zero_blur.npz / pnp_traj_laplace_zero_blur.npz     PNP_FLOW.solve_ip, tiny4, 10 x 2
   ot_ode_traj_zero_blur.npz                                   OT_ODE.solve_ip, tiny4, B = 2, 10 steps from 0.3, sigma 0.2, gamma constant: first
                           two iterates, last iterate, the Krylov vectors of every GMRES call (all below the cap of 100: asserted)
@@ -64,6 +67,86 @@ def gen_gmres(degr, utils):
         print(f"gmres case {tag}: iterations {its} (fp64 {its64.tolist()}), max|ref32 - fp64| = {dist:.3e}, max|sol| = {np.abs(sol64).max():.3e}")
     assert len(set(rec["iters_A"][:2].tolist())) == 2 and max(rec["iters_A"]) < 100 and rec["iters_A"][2] == 0
     np.savez_compressed(os.path.join(OUT, "zero_blur_gmres.npz"), **rec)
+
+
+def ref_closures(degr, utils, name):
+    """(H, H_adj) on (1, C, H, W) fp32 CPU tensors of image b -> closures(b): the reference's own degradation class where it has one for the case's
+    operator, fp32 torch forms of the same operator otherwise"""
+    import torch.nn.functional as F
+    import krylov_reference as K
+    c = K.CASES[name]
+    B, C, Hh, Ww = c["shape"]
+    kind = c["kind"]
+    if kind == 0:
+        d = degr.Denoising()
+        return lambda b: (d.H, d.H_adj)
+    if kind == 1:
+        d = degr.BoxInpainting(c["half"])
+        return lambda b: (d.H, d.H_adj)
+    if kind == 2:            # RandomInpainting draws its own mask from the batch shape on every call: a given per-image mask has no class
+        m = torch.from_numpy(K.mask_of(c).astype(np.float32))
+        return lambda b: ((lambda x: m[b][None, None] * x),) * 2
+    if kind == 6:            # (dim_image only sizes the circular mode's filter, which must hold the kernel)
+        d = degr.GaussianDeblurring(c["blur"], 61, "spatial", C, 128, "cpu")
+        return lambda b: (d.H, d.H_adj)
+    if kind == 7 and Hh == Ww:      # the reference's circular pair with `.kernel` / `.filter` holding the PSF (make_golden_psf.py)
+        k = torch.from_numpy(K.taps_of(c))
+        Kk = k.shape[0]
+        d = degr.GaussianDeblurring(1.0, Kk, "fft", C, Hh, "cpu")
+        f = torch.zeros((1, C, Hh, Ww)); f[..., :Kk, :Kk] = k
+        d.kernel = k; d.filter = torch.roll(f, shifts=(-(Kk - 1) // 2, -(Kk - 1) // 2), dims=(2, 3))
+        return lambda b: (d.H, d.H_adj)
+    if kind == 4:            # not square: the class's filter is dim x dim.  The same FFT pair on the reference's own 2-D kernel
+        k = utils.gaussian_2d_kernel(c["blur"], 61)
+        f = torch.zeros((1, C, Hh, Ww)); f[..., :61, :61] = k
+        ff = torch.fft.fft2(torch.roll(f, shifts=(-30, -30), dims=(2, 3)))
+        return lambda b: ((lambda x: torch.real(torch.fft.ifft2(torch.fft.fft2(x) * ff))), (lambda x: torch.real(torch.fft.ifft2(torch.fft.fft2(x) * torch.conj(ff)))))
+    if kind == 8:            # the reference's spatial H_adj is the correlation again, not the adjoint of an asymmetric kernel: conv2d with the flipped kernel
+        k = torch.from_numpy(K.taps_of(c))[None, None].repeat(C, 1, 1, 1)
+        return lambda b: ((lambda x: F.conv2d(x, k, padding="same", groups=C)), (lambda x: F.conv2d(x, torch.flip(k, dims=(2, 3)), padding="same", groups=C)))
+    raise ValueError(name)
+
+
+def gen_gmres_paths(degr, utils):
+    """tests/golden/krylov_paths.npz.  Asserts what tests/test_gpu_krylov_paths.py relies on, so that the reference alone satisfies each condition."""
+    import krylov_reference as K
+    rec = {}
+    for name, c in K.CASES.items():
+        B = c["shape"][0]
+        rhs = torch.from_numpy(np.array(K.rhs(name)))
+        rt2 = torch.from_numpy(K.rt2_of(name))
+        sigma2 = float(np.float32(c["sigma2"]))
+        closures = ref_closures(degr, utils, name)
+        sols, its = [], []
+        for i in range(B):
+            Hf, Ha = closures(i)
+
+            def C_ope(z, i=i, Hf=Hf, Ha=Ha):        # ot_ode.py:121-124
+                z = z.reshape(rhs.shape[1:]).unsqueeze(0)
+                return (rt2[i].unsqueeze(0) * Hf(Ha(z)) + sigma2 * z).reshape(-1)
+            out = utils.GMRES(C_ope, rhs[i].reshape(-1), max_iter=c["max_iter"], tol=K.TOL, atol=K.ATOL)
+            if isinstance(out, tuple):
+                sols.append(out[0].reshape(rhs.shape[1:]).numpy()); its.append(out[1][0] + 1)
+            else:                                    # |b| < 1e-8: b itself (utils.py:995-996)
+                sols.append(out.reshape(rhs.shape[1:]).numpy()); its.append(0)
+        sol32, its = np.stack(sols).astype(np.float64), np.array(its)
+        sol64, its64 = K.gmres64(name)
+        target = sol64 if c["capped"] else K.exact(name)
+        per = lambda a: np.abs(a).reshape(B, -1).max(axis=1)
+        dref, solmax = per(sol32 - target), per(target)
+        ret = K.returns_rhs(name)
+        dref[ret] = 0.0                              # (the right-hand side is returned: compared bit for bit, not with the solution)
+        print(f"gmres_paths {name}: vectors {its.tolist()} (fp64 {its64.tolist()}), d_ref {['%.3e' % v for v in dref]}, max|sol| {['%.3e' % v for v in solmax]}")
+        assert np.array_equal(its == 0, ret) and np.array_equal(its64 == 0, ret), (name, its, its64)
+        if c["capped"]:
+            assert (its == c["max_iter"]).all() and (its64 == c["max_iter"]).all(), (name, its, its64)
+        else:
+            assert its.max() < c["max_iter"] and its64.max() < c["max_iter"], (name, its, its64)
+            if c["counts"]:
+                assert np.abs(its - its64).max() <= 1, (name, its, its64)
+        rec[f"{name}_iters32"], rec[f"{name}_iters64"], rec[f"{name}_dref"], rec[f"{name}_solmax"] = its, its64, dref, solmax
+    assert sorted(rec) == K.fixture_keys()
+    np.savez_compressed(os.path.join(OUT, "krylov_paths.npz"), **rec)
 
 
 def gen_pnp(models, degr, utils, pnp):
@@ -170,6 +253,8 @@ if __name__ == "__main__":
         gen_op(degr)
     if "gmres" in which:
         gen_gmres(degr, utils)
+    if "gmres_paths" in which:
+        gen_gmres_paths(degr, utils)
     if "pnp" in which:
         gen_pnp(models, degr, utils, pnp)
     if "ot_ode" in which:
