@@ -21,7 +21,7 @@
 //     step s >= 2            [B(c,s)][B(c,s+1)][B(c,s+2)]                         wait vmcnt(2 NB)
 // (NB = loads per fragment step, IPW = DMA instructions per wave and chunk; the last chunk issues no DMA and waits vmcnt(2 NB)).
 //
-// Epilogue (bias / time embedding / residual / statistics / fused GroupNorm-backward first stage) is conv_mfma16.hip's.
+// Epilogue (bias / time embedding / residual / statistics) is conv_mfma16.hip's, without its fused GroupNorm-backward first stage.
 //
 // UP = 2 (round 6): the nearest-x2 upsampling conv (models.py:70-91: F.interpolate(scale 2, nearest) then a 3x3 conv) in its PHASE form.  Output
 // pixel (2i + dy, 2j + dx) reads upsampled rows 2i + dy - 1 .. 2i + dy + 1 = source rows {i-1, i, i} (dy = 0) / {i, i, i+1} (dy = 1), so each of the
@@ -31,10 +31,8 @@
 // (row + ty + dy, col + tx + dx) and it writes pixel (2 row + dy, 2 col + dx).  The image border needs no case: the taps that fall outside the
 // upsampled image are exactly the ones whose source pixel is outside the source image (zero border records).
 // Reference: the convolutions of pnpflow/models.py:94-113 (ResidualBlock), :145-162 (SelfAttention 1x1), :70-91 (Upsample).
-#include <cstdlib>
 #include <type_traits>
 #include "pf_common.h"
-
 
 namespace pf {
 
@@ -148,6 +146,9 @@ __device__ __forceinline__ void glds16(unsigned voff, const char* sbase, unsigne
 
 template <int MT, int NT, int WM, int WN, int UP, int TERMS, bool GNB>
 __global__ __launch_bounds__(256, 3) void conv_dma_kernel(const ConvParams p) {
+    // (GNB: the GroupNorm-backward epilogue this kernel once had.  No plan could reach it - conv_route.h keeps such launches on conv_mfma16 - so its
+    //  code is gone; the parameter stays, always false, so that the kernels keep the names that profiles and traces know them by)
+    static_assert(!GNB, "conv_dma has no GroupNorm-backward epilogue");
     static_assert(NT == 1, "one 32-channel N-tile per wave (the weight ring is sized for it)");
     static_assert(WM * WN == 4, "4 waves per workgroup");
     constexpr int KC = TERMS == 3 ? 32 : 64;     // channels per chunk = one 128-byte record per pixel
@@ -348,7 +349,7 @@ __global__ __launch_bounds__(256, 3) void conv_dma_kernel(const ConvParams p) {
             si = nsi; ch = nch; cur ^= 1;
         }
     }
-    // 9-tap segments first (conv_dma_supported orders them so), then the 1-tap ones: two loops, one body each
+    // 9-tap segments first (conv_route.h, dma_ok, admits no other order), then the 1-tap ones: two loops, one body each
     while (more && p.seg[si].taps == 9) {
         if (ch == 0 && si > 0) rescale(si);
         int nsi = si, nch = ch + 1;
@@ -388,32 +389,10 @@ __global__ __launch_bounds__(256, 3) void conv_dma_kernel(const ConvParams p) {
         const int n4 = ncol + cq * 4;
         const bool nok4 = n4 < p.Cout;
         float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
-        float4 g_mu, g_rs, g_ga, g_be;
-        if constexpr (GNB) {
-            const int gc = p.gnb_coff + min(n4, p.Cout - 4);
-            g_mu = *reinterpret_cast<const float4*>(p.gnb_mu + (size_t)b * p.gnb_Ct + gc);
-            g_rs = *reinterpret_cast<const float4*>(p.gnb_rs + (size_t)b * p.gnb_Ct + gc);
-            g_ga = *reinterpret_cast<const float4*>(p.gnb_gamma + gc);
-            g_be = *reinterpret_cast<const float4*>(p.gnb_beta + gc);
-        }
-        constexpr int RG = (MT >= 2 && !GNB) ? 2 : 1;      // (GNB: a second set of residual + GroupNorm-input registers spills at the 168-register bound)
+        constexpr int RG = MT >= 2 ? 2 : 1;
         float4 rv[RG][4];
-        float4 xv[GNB ? RG : 1][4];
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-            if constexpr (GNB) {
-                if (mt % RG == 0) {
-#pragma unroll
-                    for (int g = 0; g < RG; ++g)
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            const int px = (lane >> 3) + 8 * i;
-                            const int oy = min(oy0 + (wm * MT + mt + g) * 2 + (px >> 4), p.H - 1), ox = min(ox0 + (px & 15), p.W - 1);
-                            const size_t pix = ((size_t)b * p.H + oy) * p.W + ox;
-                            xv[g][i] = *reinterpret_cast<const float4*>(p.gnb_x + pix * p.gnb_xstride + min(n4, p.Cout - 4));
-                        }
-                }
-            }
             if (mt % RG == 0 && p.residual != nullptr) {
 #pragma unroll
                 for (int g = 0; g < RG; ++g)
@@ -445,36 +424,16 @@ __global__ __launch_bounds__(256, 3) void conv_dma_kernel(const ConvParams p) {
                         const float rsc = p.res_scale;
                         v.x = fmaf(rv[mt % RG][i].x, rsc, v.x); v.y = fmaf(rv[mt % RG][i].y, rsc, v.y); v.z = fmaf(rv[mt % RG][i].z, rsc, v.z); v.w = fmaf(rv[mt % RG][i].w, rsc, v.w);
                     }
-                    if constexpr (GNB) {
-                        // dyhat = da * act'(u) * gamma,  u = gamma*yhat + beta,  yhat = (x - mu)*rstd   (same expressions as gn_bwd_pre_kernel)
-                        const float4 xx = xv[mt % RG][i];
-                        float d[4] = {v.x, v.y, v.z, v.w};
-                        const float xs[4] = {xx.x, xx.y, xx.z, xx.w}, mm[4] = {g_mu.x, g_mu.y, g_mu.z, g_mu.w}, rr[4] = {g_rs.x, g_rs.y, g_rs.z, g_rs.w};
-                        const float gg[4] = {g_ga.x, g_ga.y, g_ga.z, g_ga.w}, bb[4] = {g_be.x, g_be.y, g_be.z, g_be.w};
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const float yh = (xs[j] - mm[j]) * rr[j];
-                            if (p.gnb_silu) {
-                                const float u = yh * gg[j] + bb[j];
-                                const float sgm = __builtin_amdgcn_rcpf(1.0f + __expf(-u));
-                                d[j] *= sgm * (1.0f + u * (1.0f - sgm));
-                            }
-                            d[j] *= gg[j];
-                            s1[j] += d[j]; s2[j] += d[j] * yh;
-                        }
-                        *reinterpret_cast<float4*>(p.out + pix * p.out_cstride + n4) = make_float4(d[0], d[1], d[2], d[3]);
-                    } else {
-                        *reinterpret_cast<float4*>(p.out + pix * p.out_cstride + n4) = (p.pack_from_p1 != 0 && n4 >= p.pack_from_p1 - 1) ? pack_hilo4(v) : v;
-                        s1[0] += v.x; s1[1] += v.y; s1[2] += v.z; s1[3] += v.w;
-                        s2[0] += v.x * v.x; s2[1] += v.y * v.y; s2[2] += v.z * v.z; s2[3] += v.w * v.w;
-                    }
+                    *reinterpret_cast<float4*>(p.out + pix * p.out_cstride + n4) = (p.pack_from_p1 != 0 && n4 >= p.pack_from_p1 - 1) ? pack_hilo4(v) : v;
+                    s1[0] += v.x; s1[1] += v.y; s1[2] += v.z; s1[3] += v.w;
+                    s2[0] += v.x * v.x; s2[1] += v.y * v.y; s2[2] += v.z * v.z; s2[3] += v.w * v.w;
                 }
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             __builtin_amdgcn_wave_barrier();            // scratch is rewritten by the next tile
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         }
-        if (GNB || p.stats_out != nullptr) {
+        if (p.stats_out != nullptr) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
 #pragma unroll
@@ -489,7 +448,7 @@ __global__ __launch_bounds__(256, 3) void conv_dma_kernel(const ConvParams p) {
             }
         }
     }
-    if (GNB || p.stats_out != nullptr) {
+    if (p.stats_out != nullptr) {
         __syncthreads();
         for (int t = tid; t < BN * 2; t += 256) {
             const int col = t >> 1, which = t & 1;
@@ -497,86 +456,17 @@ __global__ __launch_bounds__(256, 3) void conv_dma_kernel(const ConvParams p) {
 #pragma unroll
             for (int w = 0; w < WM; ++w) tot += s_red[(w * BN + col) * 2 + which];
             const int n = UP == 2 ? (n0 + col) % p.Cout : n0 + col;      // (UP = 2: the four phases add into the same channel)
-            if (n < p.Cout) {
-                if constexpr (GNB) unsafeAtomicAdd(p.gnb_sum + ((size_t)b * p.gnb_Ct + p.gnb_coff + n) * 2 + which, (double)tot);
-                else unsafeAtomicAdd(p.stats_out + ((size_t)b * p.Cout + n) * 2 + which, (double)tot);
-            }
+            if (n < p.Cout) unsafeAtomicAdd(p.stats_out + ((size_t)b * p.Cout + n) * 2 + which, (double)tot);
         }
     }
 }
 
-// tile of the only instantiated shape: 8 x 16 pixels x 128 output channels (4 M-tiles per weight fragment, one N-tile per wave)
-static constexpr int DMA_TH = 8, DMA_BN = 128;
-
-static int dma_mode() {      // PNPFLOW_HIP_DMA: 0 off, 1 (default) where the grid fills the chip, 2 wherever the shape is supported (tests)
-    static const int m = getenv("PNPFLOW_HIP_DMA") ? atoi(getenv("PNPFLOW_HIP_DMA")) : 1;
-    return m;
-}
-
-// the phase form of the nearest-x2 upsampling conv (UP = 2): shape test (what the engine asks before it builds the 4-phase 2 x 2 weight images) ...
-bool conv_dma_phase_shape_ok(const ConvParams& p, int terms) {
-    static const int mode = getenv("PNPFLOW_HIP_UPPHASE") ? atoi(getenv("PNPFLOW_HIP_UPPHASE")) : 1;      // test-only A/B switch: 0 = the 9-tap form on the upsampled view
-    if (mode == 0 || dma_mode() == 0 || p.nseg != 1 || p.residual != nullptr || p.gnb_x != nullptr) return false;
-    if (p.H != 2 * p.Hs || p.W != 2 * p.Ws || p.Hs % DMA_TH != 0 || p.Ws % 16 != 0 || p.Cout % 32 != 0 || (4 * p.Cout) % DMA_BN != 0) return false;
-    if (p.seg[0].w_mode != 0 || p.seg[0].C % (terms == 3 ? 32 : 64) != 0) return false;
-    if ((size_t)(p.Hs + 2) * (p.Ws + 2) * 128 >= (1ull << 31)) return false;
-    if (dma_mode() >= 2) return true;
-    return (long)p.B * (p.Hs / DMA_TH) * (p.Ws / 16) * (4 * p.Cout / DMA_BN) >= 512;
-}
-// ... and the launch test: one raw segment of taps = 4 that carries the packed phase image
-static bool conv_dma_phase_supported(const ConvParams& p, int terms) {
-    return conv_dma_phase_shape_ok(p, terms) && p.seg[0].taps == 4 && (terms == 3 ? p.seg[0].w16 : p.seg[0].w16h) != nullptr;
-}
-
-bool conv_dma_supported(const ConvParams& p, int stride, int up, int terms) {
-    if (dma_mode() == 0 || stride != 1 || (up != 0 && up != 1 && up != 2)) return false;
-    if (up == 2) return conv_dma_phase_supported(p, terms);
-    if (p.Cout % DMA_BN != 0 || p.H % DMA_TH != 0 || p.W % 16 != 0) return false;
-    if (up == 1 && (p.H != 2 * p.Hs || p.W != 2 * p.Ws)) return false;
-    if (up == 0 && (p.H != p.Hs || p.W != p.Ws)) return false;
-    const int kc = terms == 3 ? 32 : 64;
-    for (int i = 1; i < p.nseg; ++i) if (p.seg[i].taps == 9 && p.seg[i - 1].taps == 1) return false;     // ring phase: 9-tap chunks run at phase 0
-    for (int i = 0; i < p.nseg; ++i) {
-        const ConvSeg& s = p.seg[i];
-        if (s.w_mode != 0 || (terms == 3 ? s.w16 : s.w16h) == nullptr) return false;
-        if (s.C % kc != 0 || (s.taps != 9 && s.taps != 1)) return false;
-    }
-    if ((size_t)(p.Hs + 2) * (p.Ws + 2) * 128 >= (1ull << 31)) return false;     // 32-bit piece offsets inside a plane
-    if (dma_mode() >= 2) return true;
-    const long wgs = (long)p.B * (p.H / DMA_TH) * (p.W / 16) * (p.Cout / DMA_BN);
-    if (wgs < 512) return false;
-    // The prep pass costs one read + one write of every operand element (measured: 30 us on average, 8 % of a forward when every
-    // qualifying launch took this path - profiles/r03_ab_dma_variants.md), the conv it feeds is ~15 % faster than the register-staged
-    // kernel.  It pays where a prepped element feeds enough multiply-adds: MACs per operand element = K_total * Cout / (channels
-    // prepped per output pixel).  Same-box layer table: 2304 (16^2 x 256, one or two 3x3 segments) and the upsampling convs (operand
-    // at quarter resolution) win, 1152 (32^2 x 128) and the launches that drag 1-tap shortcut segments along lose; the pure 1x1
-    // launches win when Cout >= 3 C (q,k,v stacked), not at Cout = C.
-    constexpr double min_ratio = 2000.0;      // (frozen in round 5: it was an environment knob while the layer table was measured)
-    double macs = 0.0, elts = 0.0; bool all1 = true;
-    for (int i = 0; i < p.nseg; ++i) { macs += (double)p.seg[i].taps * p.seg[i].C * p.Cout; elts += p.seg[i].C; all1 &= p.seg[i].taps == 1; }
-    if (up) elts *= 0.25;
-    if (all1) return p.Cout >= 3 * (int)elts;
-    return macs / elts >= min_ratio;
-}
+// ---- host side: the only instantiated tile is DMA_TH x 16 pixels x DMA_BN output channels (conv_route.h); a route selects UP and TERMS --------
 
 template <int UP, int TERMS>
-static hipError_t launch_dma_t(const ConvParams& p, hipStream_t stream) {
-    constexpr int MT = 4, WM = 1, WN = 4;
-    constexpr int PH = DMA_TH + 2, PW = 18, NINST = (PH * PW * 8 + 63) / 64, IPW = (NINST + 3) / 4, BUF = IPW * 4 * 1024;
-    const size_t lds = 2 * BUF;
-    const int tiles = UP == 2 ? p.B * (p.Hs / DMA_TH) * (p.Ws / 16) : p.B * (p.H / DMA_TH) * (p.W / 16);
-    dim3 grid(tiles, (UP == 2 ? 4 * p.Cout : p.Cout) / DMA_BN);
-    ConvParams pp = p; pp.xcd_map = 0;
-    if (((long)grid.x * grid.y) % 8 == 0) { pp.xcd_map = 1; grid = dim3(grid.x * grid.y, 1); }
-    if (p.gnb_x != nullptr) {
-        if constexpr (UP == 0) {
-            hipLaunchKernelGGL((conv_dma_kernel<MT, 1, WM, WN, UP, TERMS, true>), grid, dim3(256), lds, stream, pp);
-            return hipGetLastError();
-        } else {
-            return hipErrorInvalidValue;
-        }
-    }
-    hipLaunchKernelGGL((conv_dma_kernel<MT, 1, WM, WN, UP, TERMS, false>), grid, dim3(256), lds, stream, pp);
+static hipError_t launch_dma_t(const ConvParams& p, const ConvRoute& r, hipStream_t stream) {
+    ConvParams pp = p; pp.xcd_map = r.xcd_map;
+    hipLaunchKernelGGL((conv_dma_kernel<4, 1, 1, 4, UP, TERMS, false>), dim3(r.grid_x, r.grid_y), dim3(256), r.lds_bytes, stream, pp);
     return hipGetLastError();
 }
 
@@ -584,11 +474,18 @@ size_t conv_dma_a16_bytes(int B, int C, int Hs, int Ws, int terms) {
     return (size_t)B * C * (Hs + 2) * (Ws + 2) * (terms == 3 ? 4 : 2);
 }
 
-hipError_t launch_conv_dma(const ConvParams& p, int up, hipStream_t s, int terms) {
+hipError_t launch_conv_dma(const ConvParams& p, const ConvRoute& r, hipStream_t s) {
+    if (r.family != ConvFamily::DMA || r.gnb || r.MT != 4 || r.NT != 1 || r.WM != 1 || r.WN != 4) return hipErrorInvalidValue;
     for (int i = 0; i < p.nseg; ++i) if (p.seg[i].a16 == nullptr) return hipErrorInvalidValue;
-    if (up == 2) return terms == 3 ? launch_dma_t<2, 3>(p, s) : launch_dma_t<2, 1>(p, s);
-    if (terms == 3) return up ? launch_dma_t<1, 3>(p, s) : launch_dma_t<0, 3>(p, s);
-    return up ? launch_dma_t<1, 1>(p, s) : launch_dma_t<0, 1>(p, s);
+    switch (r.UP * 10 + r.terms) {
+        case 3: return launch_dma_t<0, 3>(p, r, s);
+        case 13: return launch_dma_t<1, 3>(p, r, s);
+        case 23: return launch_dma_t<2, 3>(p, r, s);
+        case 1: return launch_dma_t<0, 1>(p, r, s);
+        case 11: return launch_dma_t<1, 1>(p, r, s);
+        case 21: return launch_dma_t<2, 1>(p, r, s);
+        default: return hipErrorInvalidValue;
+    }
 }
 
 }  // namespace pf

@@ -25,7 +25,6 @@
 //      (fp32 MFMA consumes 2 KiB of operands per 1024 MFMA cycles per wave: the weights
 //      stay L2/L1 resident and need no LDS staging, which leaves LDS to the patch and
 //      lets 3-6 workgroups share a CU.)
-#include <cstdlib>
 #include "pf_common.h"
 
 namespace pf {
@@ -307,60 +306,39 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvParams p) {
     }
 }
 
+// ---- host side: dispatch of a ConvRoute (conv_route.h decides tile, chunk width, grid and LDS) to its instantiation ---------------------
+
 template <int MT, int NT, int WM, int WN, int S, int UP, int BM, int KC>
-static hipError_t launch_cfg(const ConvParams& p, hipStream_t stream) {
-    constexpr int KCP = KC + 4;
-    constexpr int TH = 2 * MT * WM, TW = 16;
-    constexpr int PP = ((TH - 1) * S + 3) * ((TW - 1) * S + 3);
-    constexpr int BN = WN * NT * 32;
-    constexpr int EPI = 4 * 32 * 36 + WM * BN * 2;
-    const size_t lds = (size_t)((PP * KCP > EPI ? PP * KCP : EPI) + 2 * ((p.gn_C + 3) & ~3)) * sizeof(float);
+static hipError_t launch_cfg(const ConvParams& p, const ConvRoute& r, hipStream_t stream) {
     static unsigned long long attr_set = 0ull;
     auto kern = conv_mfma_kernel<MT, NT, WM, WN, S, UP, BM, KC>;
-    { hipError_t e = set_max_dynamic_lds_once(reinterpret_cast<const void*>(kern), attr_set, 160 * 1024); if (e != hipSuccess) return e; }
-    const int tiles = p.B * ((p.H + TH - 1) / TH) * ((p.W + TW - 1) / TW);
-    dim3 grid(tiles, (p.Cout + BN - 1) / BN);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, p);
+    { hipError_t e = set_max_dynamic_lds_once(reinterpret_cast<const void*>(kern), attr_set, ROUTE_LDS_MAX); if (e != hipSuccess) return e; }
+    hipLaunchKernelGGL(kern, dim3(r.grid_x, r.grid_y), dim3(256), r.lds_bytes, stream, p);
     return hipGetLastError();
 }
 
-static long wg_count(const ConvParams& p, int TH, int BN) {
-    return (long)p.B * ((p.H + TH - 1) / TH) * ((p.W + 15) / 16) * ((p.Cout + BN - 1) / BN);
-}
-
+// the tiles of conv_route.h's conv_mfma ladders (every form is built with every tile, the stride-2 forms included)
 template <int S, int UP, int BM, int KC>
-static hipError_t launch_sel(const ConvParams& p, hipStream_t stream) {
-    constexpr long MIN_WGS = 512;   // >= 2 workgroups per CU (a constant: finer tiles measured 12 % slower per unit of work, round 3)
-    if (S == 1) {
-        if (p.Cout <= 32) return launch_cfg<2, 1, 4, 1, S, UP, BM, KC>(p, stream);                                    // 16x16 px x 32
-        if (p.Cout <= 64 && wg_count(p, 16, 64) >= MIN_WGS) return launch_cfg<2, 2, 4, 1, S, UP, BM, KC>(p, stream);  // 16x16 px x 64
-        if (p.Cout > 64 && wg_count(p, 8, 128) >= MIN_WGS) return launch_cfg<2, 2, 2, 2, S, UP, BM, KC>(p, stream);   // 8x16 px x 128
-        if (p.Cout > 64 && wg_count(p, 4, 128) >= MIN_WGS) return launch_cfg<1, 2, 2, 2, S, UP, BM, KC>(p, stream);   // 4x16 px x 128
-        if (wg_count(p, 8, 64) >= MIN_WGS) return launch_cfg<1, 2, 4, 1, S, UP, BM, KC>(p, stream);                   // 8x16 px x 64
-        return launch_cfg<1, 1, 2, 2, S, UP, BM, KC>(p, stream);                                                      // 4x16 px x 64
-    } else {
-        if (p.Cout <= 32) return launch_cfg<1, 1, 4, 1, S, UP, BM, KC>(p, stream);                                    // 8x16 px x 32
-        if (p.Cout <= 64) return launch_cfg<1, 2, 4, 1, S, UP, BM, KC>(p, stream);                                    // 8x16 px x 64
-        return launch_cfg<1, 1, 2, 2, S, UP, BM, KC>(p, stream);                                                      // 4x16 px x 64
-    }
+static hipError_t launch_tile(const ConvParams& p, const ConvRoute& r, hipStream_t stream) {
+#define PF_TILE(mt, nt, wm, wn) if (r.MT == mt && r.NT == nt && r.WM == wm && r.WN == wn) return launch_cfg<mt, nt, wm, wn, S, UP, BM, KC>(p, r, stream)
+    PF_TILE(2, 1, 4, 1); PF_TILE(2, 2, 4, 1); PF_TILE(2, 2, 2, 2); PF_TILE(1, 2, 2, 2); PF_TILE(1, 2, 4, 1); PF_TILE(1, 1, 2, 2); PF_TILE(1, 1, 4, 1);
+#undef PF_TILE
+    return hipErrorInvalidValue;
 }
 
-hipError_t launch_conv(const ConvParams& p, int stride, int up, hipStream_t stream) {
-    bool generic = false;
-    for (int i = 0; i < p.nseg; ++i) generic |= p.seg[i].w_mode != 0;
-    if (generic) {
-        for (int i = 0; i < p.nseg; ++i) if (p.seg[i].w_mode == 0) return hipErrorInvalidValue;   // not mixed
-        if (stride != 1 || up) return hipErrorInvalidValue;
+hipError_t launch_conv(const ConvParams& p, const ConvRoute& r, hipStream_t stream) {
+    if (r.family != ConvFamily::MFMA32) return hipErrorInvalidValue;
+    const int key = r.S * 10000 + r.UP * 1000 + r.BM * 100 + r.KC;
+    switch (key) {
+        case 10164: return launch_tile<1, 0, 1, 64>(p, r, stream);
+        case 10064: return launch_tile<1, 0, 0, 64>(p, r, stream);
+        case 10116: return launch_tile<1, 0, 1, 16>(p, r, stream);
+        case 20016: return launch_tile<2, 0, 0, 16>(p, r, stream);
+        case 12016: return launch_tile<1, 2, 0, 16>(p, r, stream);
+        case 11016: return launch_tile<1, 1, 0, 16>(p, r, stream);
+        case 10016: return launch_tile<1, 0, 0, 16>(p, r, stream);
+        default: return hipErrorInvalidValue;
     }
-    bool all_1tap = true;
-    // 64-channel chunks: the generic operand clamps its k index, the packed weights end at C/16 slices and need whole chunks
-    for (int i = 0; i < p.nseg; ++i) all_1tap &= p.seg[i].taps == 1 && (generic ? p.seg[i].C >= 64 : p.seg[i].C % 64 == 0);
-    if (all_1tap && stride == 1 && !up) return generic ? launch_sel<1, 0, 1, 64>(p, stream) : launch_sel<1, 0, 0, 64>(p, stream);
-    if (generic) return launch_sel<1, 0, 1, 16>(p, stream);
-    if (stride == 2) return launch_sel<2, 0, 0, 16>(p, stream);
-    if (up == 2) return launch_sel<1, 2, 0, 16>(p, stream);
-    if (up) return launch_sel<1, 1, 0, 16>(p, stream);
-    return launch_sel<1, 0, 0, 16>(p, stream);
 }
 
 size_t conv_flops(const ConvParams& p) {

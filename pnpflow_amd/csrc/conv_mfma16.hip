@@ -14,7 +14,6 @@
 //     into a register ring two steps ahead of their use (as in conv_mfma.hip).  At this MFMA rate the
 //     weight stream is 16/3 x denser per matrix-pipe cycle than in the fp32 kernel, so the tile shapes
 //     give every wave 4 (or 2) M-tiles per N-tile: one B fragment pair feeds 12 (6) MFMAs.
-#include <cstdlib>
 #include "pp_common.h"
 
 namespace pf {
@@ -407,87 +406,56 @@ __global__ __launch_bounds__(256, conv16_lb(MT, WM, KC)) void conv_mfma16_kernel
     }
 }
 
-template <int MT, int NT, int WM, int WN, int S, int UP, int KC, int TERMS>
-static hipError_t launch_cfg16(const ConvParams& p, hipStream_t stream) {
-    constexpr int ROW = (TERMS == 3 ? KC : KC / 2) + 4;
-    constexpr int TH = 2 * MT * WM, TW = 16;
-    constexpr int HALO = KC == 64 ? 0 : 1;
-    constexpr int PH = (TH - 1) * S + 1 + 2 * HALO, PW = (TW - 1) * S + 1 + 2 * HALO;
-    constexpr int RS = ((PW * ROW + 63) / 64) * 64;
-    constexpr int BN = WN * NT * 32;
-    constexpr int EPI = 4 * 32 * 36 + WM * BN * 2;           // epilogue: 4 per-wave transpose tiles + statistics scratch (floats)
-    const size_t lds = (size_t)((PH * RS > EPI ? PH * RS : EPI) + 2 * ((p.gn_C + 3) & ~3)) * 4;
-    const int tiles = p.B * ((p.H + TH - 1) / TH) * ((p.W + TW - 1) / TW);
-    dim3 grid(tiles, (p.Cout + BN - 1) / BN);
-    ConvParams pp = p; pp.xcd_map = 0;
-    if (((long)grid.x * grid.y) % 8 == 0) { pp.xcd_map = 1; grid = dim3(grid.x * grid.y, 1); }
-    if constexpr (S == 1 && UP == 0) {
-        if (p.gnb_x != nullptr) {        // adjoint conv with the fused GroupNorm-backward first stage
-            static unsigned long long attr_set_g = 0ull;
-            auto kg = conv_mfma16_kernel<MT, NT, WM, WN, S, UP, KC, true, TERMS>;
-            { hipError_t e = set_max_dynamic_lds_once(reinterpret_cast<const void*>(kg), attr_set_g, 160 * 1024); if (e != hipSuccess) return e; }
-            hipLaunchKernelGGL(kg, grid, dim3(256), lds, stream, pp);
-            return hipGetLastError();
-        }
-    }
-    if (p.gnb_x != nullptr) return hipErrorInvalidValue;
+// ---- host side: dispatch of a ConvRoute (conv_route.h decides tile, chunk width, grid and LDS) to its instantiation ---------------------
+
+template <int MT, int NT, int WM, int WN, int S, int UP, int KC, int TERMS, bool GNB>
+static hipError_t launch_kernel16(const ConvParams& p, const ConvRoute& r, hipStream_t stream) {
     static unsigned long long attr_set = 0ull;
-    auto kern = conv_mfma16_kernel<MT, NT, WM, WN, S, UP, KC, false, TERMS>;
-    { hipError_t e = set_max_dynamic_lds_once(reinterpret_cast<const void*>(kern), attr_set, 160 * 1024); if (e != hipSuccess) return e; }
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, pp);
+    auto kern = conv_mfma16_kernel<MT, NT, WM, WN, S, UP, KC, GNB, TERMS>;
+    { hipError_t e = set_max_dynamic_lds_once(reinterpret_cast<const void*>(kern), attr_set, ROUTE_LDS_MAX); if (e != hipSuccess) return e; }
+    ConvParams pp = p; pp.xcd_map = r.xcd_map;
+    hipLaunchKernelGGL(kern, dim3(r.grid_x, r.grid_y), dim3(256), r.lds_bytes, stream, pp);
     return hipGetLastError();
 }
-
-static long wg_count16(const ConvParams& p, int TH, int BN) {
-    return (long)p.B * ((p.H + TH - 1) / TH) * ((p.W + 15) / 16) * ((p.Cout + BN - 1) / BN);
+template <int MT, int NT, int WM, int WN, int S, int UP, int KC, int TERMS>
+static hipError_t launch_cfg16(const ConvParams& p, const ConvRoute& r, hipStream_t stream) {
+    if (!r.gnb) return launch_kernel16<MT, NT, WM, WN, S, UP, KC, TERMS, false>(p, r, stream);
+    // adjoint conv with the fused GroupNorm-backward first stage: built at stride 1 without upsampling only
+    if constexpr (S == 1 && UP == 0) return launch_kernel16<MT, NT, WM, WN, S, UP, KC, TERMS, true>(p, r, stream);
+    return hipErrorInvalidValue;
 }
 
+// the tiles of conv_route.h's conv_mfma16 ladders, per stride
 template <int S, int UP, int KC, int TERMS>
-static hipError_t launch_sel16(const ConvParams& p, hipStream_t stream) {
-    // >= 2 workgroups per CU; >= 4 for the pure 1x1 launches (KC = 64): four short chunks per workgroup are a latency chain (load - stage - barrier -
-    // MFMA), which more, smaller workgroups overlap better - proj_out of the 128^2 nets' attention blocks at U-Net batch 160 (16^2 x 256 -> 256): 53.9 ->
-    // 44.7 us on the 4 x 16-pixel tile (r6, same-box A/B with the threshold at 512 / 1024 / 2048 / 4096: C2 11.39 -> 11.46 images/s, C5 unchanged)
-    constexpr long MIN_WGS = KC == 64 ? 1024 : 512;
+static hipError_t launch_tile16(const ConvParams& p, const ConvRoute& r, hipStream_t stream) {
+#define PF_TILE16(mt, nt, wm, wn) if (r.MT == mt && r.NT == nt && r.WM == wm && r.WN == wn) return launch_cfg16<mt, nt, wm, wn, S, UP, KC, TERMS>(p, r, stream)
     if constexpr (S == 1) {
-        if (p.Cout <= 32) {
-            return launch_cfg16<2, 1, 4, 1, S, UP, KC, TERMS>(p, stream);                                                        // 16x16 px x 32
-        }
-        if (p.Cout <= 64) {
-            if (wg_count16(p, 16, 64) >= MIN_WGS) return launch_cfg16<4, 1, 2, 2, S, UP, KC, TERMS>(p, stream);                  // 16x16 px x 64
-            if (wg_count16(p, 8, 64) >= MIN_WGS) return launch_cfg16<2, 1, 2, 2, S, UP, KC, TERMS>(p, stream);                   // 8x16 px x 64
-            return launch_cfg16<1, 1, 2, 2, S, UP, KC, TERMS>(p, stream);                                                        // 4x16 px x 64
-        }
-        if (wg_count16(p, 8, 128) >= MIN_WGS) return launch_cfg16<4, 1, 1, 4, S, UP, KC, TERMS>(p, stream);                      // 8x16 px x 128
-        if (wg_count16(p, 4, 128) >= MIN_WGS) return launch_cfg16<2, 1, 1, 4, S, UP, KC, TERMS>(p, stream);                      // 4x16 px x 128
-        return launch_cfg16<1, 1, 2, 2, S, UP, KC, TERMS>(p, stream);                                                            // 4x16 px x 64
+        PF_TILE16(2, 1, 4, 1); PF_TILE16(4, 1, 2, 2); PF_TILE16(2, 1, 2, 2); PF_TILE16(1, 1, 2, 2); PF_TILE16(4, 1, 1, 4); PF_TILE16(2, 1, 1, 4);
     } else {
-        if (p.Cout <= 32) return launch_cfg16<1, 1, 4, 1, S, UP, KC, TERMS>(p, stream);
-        if (p.Cout <= 64) return launch_cfg16<2, 1, 2, 2, S, UP, KC, TERMS>(p, stream);
-        return launch_cfg16<1, 1, 2, 2, S, UP, KC, TERMS>(p, stream);
+        PF_TILE16(1, 1, 4, 1); PF_TILE16(2, 1, 2, 2); PF_TILE16(1, 1, 2, 2);
     }
+#undef PF_TILE16
+    return hipErrorInvalidValue;
 }
 
-// Only fragment-major packed weights (w_mode 0) with a 16-bit repack are supported; the caller keeps the
-// fp32 kernel (launch_conv) for the generic strided operands of attention.
 template <int TERMS>
-static hipError_t launch_conv16_t(const ConvParams& p, int stride, int up, hipStream_t stream) {
-    if (p.gn_C > 1024 || (p.gn_C > 0 && p.coef == nullptr)) return hipErrorInvalidValue;      // the kernel parks at most 4 x 256 GroupNorm channels
-    bool all_1tap = true;
-    for (int i = 0; i < p.nseg; ++i) {
-        if (p.seg[i].w_mode != 0 || p.seg[i].w16 == nullptr) return hipErrorInvalidValue;
-        all_1tap &= p.seg[i].taps == 1 && p.seg[i].C % 64 == 0;    // 64-channel chunks need whole chunks: the packed weights end at C/16 slices
+static hipError_t launch_conv16_t(const ConvParams& p, const ConvRoute& r, hipStream_t stream) {
+    const int key = r.S * 1000 + r.UP * 100 + r.KC;
+    switch (key) {
+        case 1064: return launch_tile16<1, 0, 64, TERMS>(p, r, stream);
+        case 2016: return launch_tile16<2, 0, 16, TERMS>(p, r, stream);
+        case 1216: return launch_tile16<1, 2, 16, TERMS>(p, r, stream);
+        case 1132: return launch_tile16<1, 1, 32, TERMS>(p, r, stream);
+        case 1116: return launch_tile16<1, 1, 16, TERMS>(p, r, stream);
+        case 1032: return launch_tile16<1, 0, 32, TERMS>(p, r, stream);
+        case 1016: return launch_tile16<1, 0, 16, TERMS>(p, r, stream);
+        default: return hipErrorInvalidValue;
     }
-    bool all32 = true;       // 32-channel chunks wherever every segment has whole ones (at the 32-channel level: whole 128-B pixel rows, -30 % HBM reads)
-    for (int i = 0; i < p.nseg; ++i) all32 &= p.seg[i].C % 32 == 0;
-    if (all_1tap && stride == 1 && !up) return launch_sel16<1, 0, 64, TERMS>(p, stream);
-    if (stride == 2) return launch_sel16<2, 0, 16, TERMS>(p, stream);
-    if (up == 2) return launch_sel16<1, 2, 16, TERMS>(p, stream);
-    if (up) return all32 ? launch_sel16<1, 1, 32, TERMS>(p, stream) : launch_sel16<1, 1, 16, TERMS>(p, stream);
-    return all32 ? launch_sel16<1, 0, 32, TERMS>(p, stream) : launch_sel16<1, 0, 16, TERMS>(p, stream);
 }
 
-hipError_t launch_conv16(const ConvParams& p, int stride, int up, hipStream_t stream, int terms) {
-    return terms == 1 ? launch_conv16_t<1>(p, stride, up, stream) : launch_conv16_t<3>(p, stride, up, stream);
+hipError_t launch_conv16(const ConvParams& p, const ConvRoute& r, hipStream_t stream) {
+    if (r.family != ConvFamily::MFMA16) return hipErrorInvalidValue;
+    return r.terms == 1 ? launch_conv16_t<1>(p, r, stream) : r.terms == 3 ? launch_conv16_t<3>(p, r, stream) : hipErrorInvalidValue;
 }
 
 }  // namespace pf

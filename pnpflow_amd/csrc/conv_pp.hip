@@ -24,17 +24,11 @@
 // LDS patch of a team: [18 x 18 pixels][8 pieces of 16 B] = (hi k0-7 | hi k8-15 | hi k16-23 | hi k24-31 | lo ...) with piece q of the
 // pixel in column c stored at slot q ^ ((c >> 1) & 7): the 16 pixels a ds_read_b128 lane group touches ({0-3, 12-15} of one tile row +
 // {4-11} of the next, shifted by the tap) land on 16 different 16-byte bank slots for every tap (the swizzle conv_dma.hip uses).
-#include <cstdlib>
 #include "pp_common.h"
 
 namespace pf {
 
-// MT = M-tiles (2 rows x 16 pixels) per wave: a team's tile is 8 MT rows x 16 columns, its halo patch (8 MT + 2) x 18 pixels x 128 B
-constexpr int PP_PW = 18;
-constexpr int pp_w9(int TERMS) { return TERMS == 3 ? 36864 : 18432; }      // LDS bytes of a 9-tap / 1-tap 32-channel chunk image ([k16-step][hi | lo] or [k16-step][hi])
-constexpr int pp_w1(int TERMS) { return TERMS == 3 ? 4096 : 2048; }
-constexpr int pp_npix(int MT) { return (8 * MT + 2) * PP_PW; }
-constexpr int pp_patch_bytes(int MT) { return pp_npix(MT) * 128; }                         // MT 1: 23 040 B, MT 2: 41 472 B per team
+// (tile and LDS arithmetic shared with the router - PP_PW, pp_w9, pp_w1, pp_npix, pp_patch_bytes, PP_MT, pp_teams, pp_structure: conv_route.h)
 constexpr int pp_a9(int MT) { return (pp_npix(MT) * 8 + 255) / 256; }                      // float4 per lane of a 9-tap chunk: 6 / 11
 
 // The K-chunk structure is compile-time: N9 nine-tap chunks (GroupNorm(+SiLU) staging) followed by N1 one-tap chunks (raw: a folded 1x1
@@ -472,85 +466,27 @@ __global__ __launch_bounds__(256 * TEAMS, 2) void conv_pp_kernel(const PPParams 
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
 
-static int ilog2_exact(int v) { int l = 0; while ((1 << l) < v) ++l; return (1 << l) == v ? l : -1; }
-
-constexpr int PP_MT = 1;      // 8 x 16-pixel team tiles: at 2 waves per SIMD two register sets of raw patch + the residual + accumulators fit 256 registers.
-                              // (16 x 16 tiles - MT = 2, 11 float4 per prefetch set - spill 57-156 registers with the two-step prefetch and measured
-                              // +30 ... +70 % per launch, r4; they would need conv_pp64's one-step re-request scheme)
-
-// chunk structures instantiated: ResidualBlock conv1 / conv2 of the down path (one 3x3 chunk, with / without the identity residual), conv1 of
-// the up path over cat[h, skip] (two / three 3x3 chunks), conv2 of the up path with the folded 1x1 shortcut (one 3x3 + two / three 1x1 chunks)
-static bool pp_structure(int n9, int n1, bool res) {
-    if (res) return n9 == 1 && n1 == 0;
-    return (n1 == 0 && n9 >= 1 && n9 <= 3) || (n9 == 1 && (n1 == 2 || n1 == 3));
-}
-
-bool conv_pp_supported(const ConvParams& p, int stride, int up, int terms) {
-    static const int mode = getenv("PNPFLOW_HIP_PP") ? atoi(getenv("PNPFLOW_HIP_PP")) : 1;      // test-only A/B switch: 0 off, 1 on, 3 on in the default mode only (mode 2 on conv_mfma16)
-    constexpr int TH = 8 * PP_MT;
-    if (mode == 0 || (terms != 3 && !(terms == 1 && mode != 3)) || stride != 1 || up != 0 || p.gnb_x != nullptr) return false;
-    if (p.Cout != 32 || p.out_cstride != 32 || (p.residual != nullptr && p.res_cstride != 32)) return false;
-    if (p.H % TH || p.W % 16 || p.Hs != p.H || p.Ws != p.W) return false;
-    if (ilog2_exact(p.H / TH) < 0 || ilog2_exact(p.W / 16) < 0) return false;
-    // a persistent grid pays its prologue (weights -> LDS per workgroup, two-step pipeline fill) over >= 32 tiles per team: measured at 256^2,
-    // B = 8 / 16 / 32 / 80 -> +11 % / +1.5 % / -1.4 % / -3 % on the whole forward; smaller launches stay on conv_mfma16
-    // (teams of the launch = 2 per CU; 32 x 512 tiles on the 256 CUs of an MI355X)
-    const int grid = persistent_grid();
-    if (grid < 8 || (long)p.B * (p.H / TH) * (p.W / 16) < 32L * 2 * grid) return false;
-    if (p.W > 2048) return false;      // patch pixel offsets py * W + px are packed into 16 bits (pk9[])
-    int n9 = 0, n1 = 0;
-    for (int i = 0; i < p.nseg; ++i) {
-        const ConvSeg& s = p.seg[i];
-        if (s.w_mode != 0 || s.w16 == nullptr || s.C % 32) return false;
-        if (s.taps == 9) { if (n1 > 0 || s.xform == 0) return false; n9 += s.C / 32; }     // 9-tap chunks are GroupNorm-ed (their coefficient loads are unconditional)
-        else if (s.taps == 1) { if (s.xform != 0) return false; n1 += s.C / 32; }
-        else return false;
-    }
-    if (!pp_structure(n9, n1, p.residual != nullptr)) return false;
-    if (p.gn_C > 0 && p.coef == nullptr) return false;
-    return (size_t)n9 * pp_w9(terms) + (size_t)n1 * pp_w1(terms) + 2 * pp_patch_bytes(PP_MT) <= 160 * 1024;
-}
-
-// TEAMS = 1: two independent 4-wave workgroups per CU (each with its own copy of the weights) where LDS allows - the teams of one
-// 8-wave workgroup wait for each other at every phase boundary, independent workgroups only for their own data (r4: 192 vs 214 us on the
-// one-chunk conv); TEAMS = 2 (one workgroup per CU, weights shared) for the structures whose weights do not fit twice
-template <int N9, int N1, bool RES, int TEAMS, int TERMS>
-static hipError_t launch_pp_tt(const PPParams& p0, hipStream_t s) {
+// One instantiation per chunk structure conv_route.h accepts (pp_structure), with the TEAMS its weights allow (pp_teams): grid and LDS are the route's
+template <int N9, int N1, bool RES, int TERMS>
+static hipError_t launch_pp_t(const PPParams& p0, const ConvRoute& r, hipStream_t s) {
+    constexpr int TEAMS = pp_teams(N9, N1, TERMS);
+    static_assert(pp_structure(N9, N1, RES), "conv_route.h never routes this chunk structure");
+    if (r.teams != TEAMS || r.grid_x <= 0) return hipErrorInvalidConfiguration;
     static unsigned long long attr_set = 0ull;
     auto kern = conv_pp_kernel<PP_MT, N9, N1, RES, TEAMS, TERMS>;
-    { hipError_t e = set_max_dynamic_lds_once(reinterpret_cast<const void*>(kern), attr_set, 160 * 1024); if (e != hipSuccess) return e; }
-    const int grid = persistent_grid() * (TEAMS == 1 ? 2 : 1);
-    if (grid <= 0) return hipErrorInvalidConfiguration;
+    { hipError_t e = set_max_dynamic_lds_once(reinterpret_cast<const void*>(kern), attr_set, ROUTE_LDS_MAX); if (e != hipSuccess) return e; }
     PPParams p = p0;
     p.lx = ilog2_exact(p.W / 16); p.ly = ilog2_exact(p.H / (8 * PP_MT));
     p.rot = 5;
-    const size_t lds = (size_t)N9 * pp_w9(TERMS) + (size_t)N1 * pp_w1(TERMS) + TEAMS * pp_patch_bytes(PP_MT);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256 * TEAMS), lds, s, p);
+    hipLaunchKernelGGL(kern, dim3(r.grid_x), dim3(256 * TEAMS), r.lds_bytes, s, p);
     return hipGetLastError();
 }
 
-template <int N9, int N1, bool RES, int TERMS>
-static hipError_t launch_pp_t(const PPParams& p, hipStream_t s) {
-    constexpr size_t one = (size_t)N9 * pp_w9(TERMS) + (size_t)N1 * pp_w1(TERMS) + pp_patch_bytes(PP_MT);
-    if constexpr (2 * one <= 160 * 1024) return launch_pp_tt<N9, N1, RES, 1, TERMS>(p, s);
-    else return launch_pp_tt<N9, N1, RES, 2, TERMS>(p, s);
-}
-
-template <int TERMS>
-static hipError_t launch_conv_pp_terms(const PPParams& p, hipStream_t s) {
-    const bool res = p.residual != nullptr;
-    if (p.n9 == 1 && p.n1 == 0) return res ? launch_pp_t<1, 0, true, TERMS>(p, s) : launch_pp_t<1, 0, false, TERMS>(p, s);
-    if (res) return hipErrorInvalidValue;
-    if (p.n9 == 2 && p.n1 == 0) return launch_pp_t<2, 0, false, TERMS>(p, s);
-    if (p.n9 == 3 && p.n1 == 0) return launch_pp_t<3, 0, false, TERMS>(p, s);
-    if (p.n9 == 1 && p.n1 == 2) return launch_pp_t<1, 2, false, TERMS>(p, s);
-    if (p.n9 == 1 && p.n1 == 3) return launch_pp_t<1, 3, false, TERMS>(p, s);
-    return hipErrorInvalidValue;
-}
-
-hipError_t launch_conv_pp(const PPParams& p, hipStream_t s, int terms) {
-    if (terms == 1) return launch_conv_pp_terms<1>(p, s);
-    if (terms == 3) return launch_conv_pp_terms<3>(p, s);
+hipError_t launch_conv_pp(const PPParams& p, const ConvRoute& r, hipStream_t s) {
+    if (r.family != ConvFamily::PP || r.n9 != p.n9 || r.n1 != p.n1 || r.res != (p.residual != nullptr) || (r.terms != 3 && r.terms != 1)) return hipErrorInvalidValue;
+#define PF_PP(n9_, n1_, res_) if (r.n9 == n9_ && r.n1 == n1_ && r.res == res_) return r.terms == 3 ? launch_pp_t<n9_, n1_, res_, 3>(p, r, s) : launch_pp_t<n9_, n1_, res_, 1>(p, r, s)
+    PF_PP(1, 0, true); PF_PP(1, 0, false); PF_PP(2, 0, false); PF_PP(3, 0, false); PF_PP(1, 2, false); PF_PP(1, 3, false);
+#undef PF_PP
     return hipErrorInvalidValue;
 }
 

@@ -24,24 +24,12 @@
 // operand scale of a chunk is fetched with the chunk's GroupNorm coefficients as a vector load.
 // vmcnt is counted by hand around the LDS-DMA pieces (memory operations return in order): pieces are issued right behind a barrier,
 // BEFORE the three patch requests of that half-chunk, and waited for with vmcnt(3) in front of the next barrier.
-#include <cstdlib>
 #include "pp_common.h"
 
 namespace pf {
 
-constexpr int SP_PITCH = 20, SP_PW = 18;
-constexpr int sp_rows(int MT) { return 8 * MT; }                                   // tile rows
-constexpr int sp_npix(int MT) { return (sp_rows(MT) + 2) * SP_PW; }
-constexpr int sp_patch(int MT) { return (sp_rows(MT) + 2) * SP_PITCH * 64; }      // MT 2: 23 040 B
+// (tile and LDS arithmetic shared with the router - SP_PITCH, SP_PW, sp_rows, sp_npix, sp_patch, sp_tap, sp_x, sp_y, SP_TAB, sp_lds: conv_route.h)
 constexpr int sp_a9(int MT) { return (sp_npix(MT) * 4 + 255) / 256; }             // float4 per lane and chunk (MT 2: 6)
-// TERMS = 3: the fp32-equivalent split; TERMS = 1 (round 6): precision mode 2 - hi-only operands, one MFMA per (M-tile, N-tile) and tap, hi-only weight
-// images (a tap is NT KiB; slot X is rounded up to whole 4 KiB refill rounds: at NT = 2 its five taps are 10 KiB and the refill fetches 12 - the two
-// extra KiB are the head of tap 5 in the chunk image, never read from X)
-constexpr int sp_tap(int NT, int TERMS = 3) { return (TERMS == 3 ? 2 : 1) * NT * 1024; }      // bytes of one tap: (hi | lo) x NT x 1 KiB
-constexpr int sp_x(int NT, int TERMS = 3) { return (5 * sp_tap(NT, TERMS) + 4095) / 4096 * 4096; }      // slot X: taps 0..4
-constexpr int sp_y(int NT, int TERMS = 3) { return 4 * sp_tap(NT, TERMS); }                  // slot Y: taps 5..8
-constexpr int SP_TAB = PP_MAXCH * 32;                                               // chunk table: 32 B per chunk (see the kernel's prologue)
-constexpr int sp_lds(int MT, int NT, int TERMS = 3) { return sp_x(NT, TERMS) + sp_y(NT, TERMS) + 2 * sp_patch(MT) + SP_TAB; }
 // the A9 float4 of the next chunk are staged under the seven taps that carry no refill (0-3, 5-7), front-loaded: with A9 = 6 one under
 // each of taps 0-3, 5, 6; with A9 = 10 two under taps 0-2 and one under taps 3, 5, 6, 7
 constexpr int sp_stage_n(int A9, int tap) {            // float4 staged under `tap`
@@ -160,7 +148,7 @@ __global__ __launch_bounds__(256, 1) void conv_sp_kernel(const PPParams p) {
         return (gptr)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)hi) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)lo));
     };
     auto describe = [&](const PPTile& tl, const Ent& e) __attribute__((always_inline)) -> Desc {
-        // (32-bit index arithmetic: conv_sp_supported bounds B H W cstride below 2^31 - the 64-bit products of the first version were a
+        // (32-bit index arithmetic: the router, conv_route.h, bounds B H W cstride below 2^31 - the 64-bit products of the first version were a
         // serial chain of ~60 scalar instructions per chunk)
         const int pix = (tl.b * p.H + tl.oy0) * p.W + tl.ox0 - p.W - 1;
         const int cstride = __builtin_amdgcn_readfirstlane((int)e.b.x), coff = __builtin_amdgcn_readfirstlane((int)e.b.y);
@@ -193,7 +181,7 @@ __global__ __launch_bounds__(256, 1) void conv_sp_kernel(const PPParams p) {
     // ~60 instructions are spread by the scheduler over the MFMA shadows of a tap (sched_group_barrier pattern below); the values are
     // those of conv_mfma16's staging (silu_pp; hi = RNE16(x), lo = RNE16(x - hi)).  Every thread stores: the threads past the end of the
     // patch (A9 * 256 > 4 NPIX) hold the clamped last pixel and write ITS values to ITS address.  The launches this kernel takes are
-    // GroupNorm + SiLU on every chunk (conv_sp_supported).
+    // GroupNorm + SiLU on every chunk (conv_route.h: sp_ok).
     auto transform_one = [&](const Coef& S, int i, unsigned pofs) __attribute__((always_inline)) {
         float4 v = ra[i];
         v.x = silu_pp(v.x * S.csc.x + S.csh.x); v.y = silu_pp(v.y * S.csc.y + S.csh.y);
@@ -255,7 +243,7 @@ __global__ __launch_bounds__(256, 1) void conv_sp_kernel(const PPParams p) {
     float addv[NT]; float oscale = 0.f;
     auto tile_inputs = [&](const PPTile& tl) __attribute__((always_inline)) {
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) addv[nt] = p.addvec[(size_t)tl.b * p.addvec_bs + hoff + nt * 32 + ch_of_col];      // (conv_sp_supported: never null - the NT loads are counted in chunk 0's vmcnt)
+        for (int nt = 0; nt < NT; ++nt) addv[nt] = p.addvec[(size_t)tl.b * p.addvec_bs + hoff + nt * 32 + ch_of_col];      // (conv_route.h, sp_ok: never null - the NT loads are counted in chunk 0's vmcnt)
         const float inv_last = scale_c[8 * tl.b + 4 + seg_id[3]];
         oscale = p.out_scale * (1.0f / 256.0f) * inv_last;
         asm volatile("" : "+v"(oscale));      // (consumed HERE: no scalar load may stay in flight into the chunk loop)
@@ -590,64 +578,30 @@ __global__ __launch_bounds__(256, 1) void conv_sp_kernel(const PPParams p) {
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
 
-static int ilog2_exact_sp(int v) { int l = 0; while ((1 << l) < v) ++l; return (1 << l) == v ? l : -1; }
-
-bool conv_sp_supported(const ConvParams& p, int stride, int up, int terms) {
-    static const int mode = getenv("PNPFLOW_HIP_SP") ? atoi(getenv("PNPFLOW_HIP_SP")) : 1;      // test-only A/B switch: 0 off, 1 on, 2 the 128-channel level only, 3 on in the default mode only, 4 as 1 but the 256-channel level stays on conv_dma
-    if (mode == 0 || (terms != 3 && !(terms == 1 && mode != 3)) || stride != 1 || up != 0 || p.gnb_x != nullptr) return false;
-    // Cout 256 (round 7): two N-halves of 128 channels (NSPLIT = 2), built for the default mode (terms 3) only
-    const int nsplit = p.Cout == 256 ? 2 : 1;
-    if (p.Cout != 128 && !(p.Cout == 64 && (mode == 1 || mode == 4)) && !(p.Cout == 256 && mode == 1 && terms == 3)) return false;
-    if (p.out_cstride != p.Cout || (p.residual != nullptr && p.res_cstride != p.Cout)) return false;
-    // the hand-counted vmcnt in front of the first barrier of a tile's chunk 0 counts the NT bias loads of tile_inputs: a launch without a
-    // bias vector would wait NT operations too loosely - such launches stay on conv_mfma16
-    if (p.addvec == nullptr) return false;
-    const int TH = p.Cout == 64 ? sp_rows(4) : sp_rows(2);      // 16 x 16-pixel workgroup tiles at 128 (and 2 x 128) channels, 32 x 16 at 64
-    if (p.H % TH || p.W % 16 || p.Hs != p.H || p.Ws != p.W) return false;
-    // the staging packs the patch-pixel offset py * W + px (py <= TH + 1, px <= 17) into 16 bits (pk[], issue_one): ADVICE r5 - the bound
-    // depends on the tile height, W <= 1024 at Cout 64 / W <= 2048 at Cout 128
-    if ((TH + 1) * p.W + SP_PW - 1 > 65535) return false;
-    if (ilog2_exact_sp(p.H / TH) < 0 || ilog2_exact_sp(p.W / 16) < 0) return false;
-    // the persistent grid pays its prologue and pipeline fill over >= 4 tiles per workgroup
-    const int grid = persistent_grid();
-    // (NSPLIT = 2: an item is a (tile, N-half); the workgroups pair up inside an XCD, so a grid of an even number of workgroups per XCD)
-    if (grid < 8 || (long)nsplit * p.B * (p.H / TH) * (p.W / 16) < 4L * grid || (nsplit == 2 && grid % 16 != 0)) return false;
-    int nch = 0;
-    for (int i = 0; i < p.nseg; ++i) {
-        const ConvSeg& s = p.seg[i];
-        if ((double)p.B * p.H * p.W * s.cstride >= 2147483648.0) return false;      // 32-bit element offsets (describe)
-        if (s.w_mode != 0 || s.w16 == nullptr || s.C % 32 || s.taps != 9 || s.xform != 2) return false;      // GroupNorm + SiLU 3x3 segments of an even number of 16-channel chunks
-        nch += s.C / 16;
-    }
-    if (nch < 2 || nch > PP_MAXCH || (nch & 1)) return false;
-    return p.gn_C > 0 && p.coef != nullptr && p.scale != nullptr;      // (with_coef: every GroupNorm-ed split-fp16 launch carries operand scales)
-}
-
 template <int MT, int NT, int TERMS, int NSPLIT = 1>
-static hipError_t launch_sp_t(const PPParams& p0, hipStream_t s) {
+static hipError_t launch_sp_t(const PPParams& p0, const ConvRoute& r, hipStream_t s) {
     static unsigned long long attr_set[2] = {0ull, 0ull};
-    const bool res = p0.residual != nullptr;
-    const void* kern = res ? reinterpret_cast<const void*>(conv_sp_kernel<MT, NT, true, TERMS, NSPLIT>) : reinterpret_cast<const void*>(conv_sp_kernel<MT, NT, false, TERMS, NSPLIT>);
-    { hipError_t e = set_max_dynamic_lds_once(kern, attr_set[res ? 1 : 0], 160 * 1024); if (e != hipSuccess) return e; }
-    const int grid = persistent_grid();
-    if (grid <= 0 || (NSPLIT == 2 && grid % 16 != 0)) return hipErrorInvalidConfiguration;
+    const void* kern = r.res ? reinterpret_cast<const void*>(conv_sp_kernel<MT, NT, true, TERMS, NSPLIT>) : reinterpret_cast<const void*>(conv_sp_kernel<MT, NT, false, TERMS, NSPLIT>);
+    { hipError_t e = set_max_dynamic_lds_once(kern, attr_set[r.res ? 1 : 0], ROUTE_LDS_MAX); if (e != hipSuccess) return e; }
+    if (r.grid_x <= 0 || (NSPLIT == 2 && r.grid_x % 16 != 0)) return hipErrorInvalidConfiguration;      // (the pairing of the N-halves reads ranks 2 k, 2 k + 1 of one XCD)
     PPParams p = p0;
-    p.lx = ilog2_exact_sp(p.W / 16); p.ly = ilog2_exact_sp(p.H / sp_rows(MT));
+    p.lx = ilog2_exact(p.W / 16); p.ly = ilog2_exact(p.H / sp_rows(MT));
     p.rot = 5;
-    if (res) hipLaunchKernelGGL((conv_sp_kernel<MT, NT, true, TERMS, NSPLIT>), dim3(grid), dim3(256), sp_lds(MT, NT, TERMS), s, p);
-    else hipLaunchKernelGGL((conv_sp_kernel<MT, NT, false, TERMS, NSPLIT>), dim3(grid), dim3(256), sp_lds(MT, NT, TERMS), s, p);
+    if (r.res) hipLaunchKernelGGL((conv_sp_kernel<MT, NT, true, TERMS, NSPLIT>), dim3(r.grid_x), dim3(256), r.lds_bytes, s, p);
+    else hipLaunchKernelGGL((conv_sp_kernel<MT, NT, false, TERMS, NSPLIT>), dim3(r.grid_x), dim3(256), r.lds_bytes, s, p);
     return hipGetLastError();
 }
 
-hipError_t launch_conv_sp(const PPParams& p0, hipStream_t s, int terms) {
-    if (p0.n9 < 2 || (p0.n9 & 1) || p0.n9 > PP_MAXCH || p0.n1 != 0 || (terms != 3 && terms != 1)) return hipErrorInvalidValue;
-    if (p0.cout == 256) {      // two N-halves of 128 channels: every chunk carries the second half's weight image
-        for (int c = 0; c < p0.n9; ++c) if (p0.wimg_h1[c] == nullptr) return hipErrorInvalidValue;
-        return terms == 3 ? launch_sp_t<2, 4, 3, 2>(p0, s) : hipErrorInvalidValue;
+hipError_t launch_conv_sp(const PPParams& p, const ConvRoute& r, hipStream_t s) {
+    if (r.family != ConvFamily::SP || r.n9 != p.n9 || p.n1 != 0 || r.res != (p.residual != nullptr)) return hipErrorInvalidValue;
+    switch (r.MT * 1000 + r.NT * 100 + r.nsplit * 10 + r.terms) {
+        case 2423: return launch_sp_t<2, 4, 3, 2>(p, r, s);      // Cout 256: two N-halves of 128 channels
+        case 2413: return launch_sp_t<2, 4, 3>(p, r, s);         // Cout 128
+        case 2411: return launch_sp_t<2, 4, 1>(p, r, s);
+        case 4213: return launch_sp_t<4, 2, 3>(p, r, s);         // Cout 64
+        case 4211: return launch_sp_t<4, 2, 1>(p, r, s);
+        default: return hipErrorInvalidValue;
     }
-    if (p0.cout == 128) return terms == 3 ? launch_sp_t<2, 4, 3>(p0, s) : launch_sp_t<2, 4, 1>(p0, s);
-    if (p0.cout == 64) return terms == 3 ? launch_sp_t<4, 2, 3>(p0, s) : launch_sp_t<4, 2, 1>(p0, s);
-    return hipErrorInvalidValue;
 }
 
 }  // namespace pf

@@ -47,9 +47,9 @@ enum OpKind { OP_MEMSET, OP_TEMB, OP_BEGIN, OP_CONV, OP_SOFTMAX, OP_ATTN, OP_STA
 struct Op {
     OpKind kind;
     ConvParams cp; int stride = 1, up = 0;
-    int dma = 0;                                    // OP_CONV: 1 = conv_dma.hip (its operands were written by the OP_PREP in front of it)
-    int terms = 0;                                  // OP_CONV: conv_terms() of the plan's precision mode - the TERMS form that matches the weight images chosen at build time
-    int use_pp = 0; PPParams ppp{};                 // OP_CONV: 1 = conv_pp.hip (persistent two-team kernel of the 32-channel level), 2 = conv_sp.hip (64- / 128-channel levels; the 256-channel level as two N-halves)
+    ConvRoute route{};                              // OP_CONV: kernel, instantiation and launch geometry, decided once at plan build (conv_route.h); route.terms is conv_terms() of the
+                                                    // plan's precision mode - the TERMS form that matches the weight images chosen at build time.  DMA: the operands were written by the OP_PREP in front
+    PPParams ppp{};                                 // OP_CONV on conv_pp.hip / conv_sp.hip: the launch as a list of K-chunks
     PrepParams pp{};
     EdgeConvParams ep;
     TembParams tp;
@@ -335,7 +335,7 @@ static wpack::Oihw oihw(pf_engine* e, const std::string& wname) {
 static std::string range_key(int lo, int hi) { return std::to_string(lo) + ":" + std::to_string(hi); }
 
 // Every packed weight image reaches the device through here: cache lookup under `key`, the packer of weight_pack.h (`pack`: () -> vector, run on a
-// miss only), upload of its bytes and - for the images attach_dma / attach_pp derive further images from - the record of the host slice it came from.
+// miss only), upload of its bytes and - for the images attach_dma / attach_pp pack further images from, and the router asks about - the record of the host slice it came from.
 template <class Pack>
 static float* weight_image(pf_engine* e, const std::string& key, Pack pack, const pf_engine::W16Src* src = nullptr) {
     auto it = e->dev.find(key);
@@ -445,28 +445,48 @@ static ConvParams with_coef(Builder& bd, ConvParams p, std::vector<Op>& ops) {
     return p;
 }
 
-// LDS-DMA path (conv_dma.hip): if the launch qualifies, the operands of its K-segments are pre-transformed by one OP_PREP in front of it
-// (after the OP_GN_COEF that finalises its GroupNorm coefficients / operand scales).  The a16 buffers are launch-local temporaries.
-static bool attach_dma(Builder& bd, ConvParams& p, int stride, int up, std::vector<Op>& ops) {
+// Kernel routing (conv_route.h).  The four test-only switches are read once per process; the persistent grid is the current device's.
+static RouteEnv route_env() {
+    static const RouteEnv switches = [] {
+        auto rd = [](const char* name) { const char* v = getenv(name); return v ? atoi(v) : 1; };
+        RouteEnv v; v.pp = rd("PNPFLOW_HIP_PP"); v.sp = rd("PNPFLOW_HIP_SP"); v.dma = rd("PNPFLOW_HIP_DMA"); v.upphase = rd("PNPFLOW_HIP_UPPHASE");
+        return v;
+    }();
+    RouteEnv v = switches; v.cu_grid = persistent_grid();
+    return v;
+}
+// the launch as conv_route() sees it: route_shape() plus, per segment, the host slice its split-fp16 image was packed from (weight_image's record) -
+// what the hi-only image of conv_dma and the LDS chunk images of conv_pp / conv_sp are packed from once the route is chosen
+static RouteShape routed_shape(pf_engine* e, const ConvParams& p) {
+    RouteShape s = route_shape(p);
+    for (int i = 0; i < p.nseg; ++i) {
+        auto it = e->w16_src.find(p.seg[i].w16);
+        if (it == e->w16_src.end()) continue;
+        const wpack::Oihw w = oihw(e, it->second.name);
+        RouteSeg& q = s.seg[i];
+        q.has_w16_src = true; q.src_lo = it->second.lo; q.src_hi = it->second.hi; q.src_O = w.O; q.src_kk = w.kk;
+    }
+    return s;
+}
+
+// A launch routed to conv_dma.hip (LDS-DMA path): the operands of its K-segments are pre-transformed by one OP_PREP in front of it (after the OP_GN_COEF
+// that finalises its GroupNorm coefficients / operand scales).  The a16 buffers are launch-local temporaries.  false: an image or a buffer could not be allocated
+static bool attach_dma(Builder& bd, ConvParams& p, const ConvRoute& r, std::vector<Op>& ops) {
     pf_engine* e = bd.e;
-    const int terms = conv_terms(e);
-    if (terms == 0) return false;
-    if (terms == 1)
+    if (r.terms == 1)
         for (int i = 0; i < p.nseg; ++i) {
-            auto it = e->w16_src.find(p.seg[i].w16);
-            if (p.seg[i].w_mode != 0 || it == e->w16_src.end()) return false;
-            if ((it->second.hi - it->second.lo) % 64 != 0) return false;
-            p.seg[i].w16h = packed_conv16(e, it->second.name, it->second.lo, it->second.hi, 1);
+            const pf_engine::W16Src& src = e->w16_src.at(p.seg[i].w16);
+            p.seg[i].w16h = packed_conv16(e, src.name, src.lo, src.hi, 1);
+            if (!p.seg[i].w16h) return false;
         }
-    if (!conv_dma_supported(p, stride, up, terms)) return false;
     Op op{}; op.kind = OP_PREP;
     PrepParams& q = op.pp;
-    q.nseg = p.nseg; q.B = p.B; q.Hs = p.Hs; q.Ws = p.Ws; q.terms = terms;
+    q.nseg = p.nseg; q.B = p.B; q.Hs = p.Hs; q.Ws = p.Ws; q.terms = r.terms;
     q.coef = p.coef; q.coef_stride = p.coef_stride; q.scale = p.scale;
     std::vector<float*> tmp;
     for (int i = 0; i < p.nseg; ++i) {
         ConvSeg& sg = p.seg[i];
-        float* a = bd.acquire(conv_dma_a16_bytes(p.B, sg.C, p.Hs, p.Ws, terms) / sizeof(float));
+        float* a = bd.acquire(conv_dma_a16_bytes(p.B, sg.C, p.Hs, p.Ws, r.terms) / sizeof(float));
         if (!a) return false;
         tmp.push_back(a);
         sg.a16 = a;
@@ -477,39 +497,33 @@ static bool attach_dma(Builder& bd, ConvParams& p, int stride, int up, std::vect
     return true;
 }
 
-// conv_pp.hip (persistent two-team kernel of the 32-channel level: 32-channel K-chunks) / conv_sp.hip (one wave per SIMD, the 64- and 128-channel
-// levels: 16-channel K-chunks, weights streamed through LDS slots): the launch becomes a list of K-chunks in the kernel argument
-static int attach_pp(Builder& bd, const ConvParams& p, int stride, int up, PPParams& q) {      // 0: no; 1: conv_pp; 2: conv_sp
+// A launch routed to conv_pp.hip (persistent two-team kernel of the 32-channel level: 32-channel K-chunks) or conv_sp.hip (one wave per SIMD, the 64- and
+// 128-channel levels: 16-channel K-chunks, weights streamed through LDS slots) becomes a list of K-chunks in the kernel argument.  false: an image could not be allocated
+static bool attach_pp(Builder& bd, const ConvParams& p, const ConvRoute& r, PPParams& q) {
     pf_engine* e = bd.e;
-    // precision mode 2 (one MFMA per product): the hi-only TERMS = 1 forms of both persistent kernels (round 6)
-    const int terms = conv_terms(e);
-    if (terms == 0) return 0;
-    const bool sp = (p.Cout == 256 || p.Cout == 128 || p.Cout == 64) && conv_sp_supported(p, stride, up, terms);
-    const int sp_nt = p.Cout == 256 ? 4 : p.Cout / 32;      // Cout 256: two N-halves of 128 channels, one image per chunk and half
-    if (!sp && !(p.Cout == 32 && conv_pp_supported(p, stride, up, terms))) return 0;
+    const bool sp = r.family == ConvFamily::SP;
+    const int terms = r.terms;      // precision mode 2 (one MFMA per product): the hi-only TERMS = 1 forms of both persistent kernels (round 6)
     q = PPParams{};
     q.cout = p.Cout;
     const int kc = sp ? 16 : 32;
     int n = 0;
     for (int i = 0; i < p.nseg; ++i) {
         const ConvSeg& sg = p.seg[i];
-        auto it = e->w16_src.find(sg.w16);
-        if (it == e->w16_src.end()) return 0;
+        const pf_engine::W16Src& src = e->w16_src.at(sg.w16);
+        const wpack::Oihw w = oihw(e, src.name);
         for (int cc = 0; cc < sg.C / kc; ++cc) {
             PPChunk& k = q.ch[n++];
             k.src = sg.src; k.cstride = sg.cstride; k.coff = sg.coff + cc * kc; k.xform = sg.xform;
             k.gn_c0 = sg.gn_off + cc * kc; k.seg = i;
             // LDS image of this chunk (weight_pack.h): conv_pp reads the split image in both modes, conv_sp the hi-only one at terms 1
-            const std::string& wn = it->second.name; const int lo = it->second.lo + cc * kc;
-            const wpack::Oihw w = oihw(e, wn);
-            if (w.O != p.Cout || (sp && w.kk != 9)) return 0;
+            const std::string& wn = src.name; const int lo = src.lo + cc * kc;
             const std::string sp_key = wn + (terms == 1 ? "#sph" : "#sp") + std::to_string(p.Cout) + "_" + std::to_string(lo);
             k.wimg = !sp ? weight_image(e, wn + "#pp" + std::to_string(lo), [&] { return wpack::chunk_pp(w, lo); })
-                         : weight_image(e, p.Cout == 256 ? sp_key + "_h0" : sp_key, [&] { return wpack::chunk_sp(w, lo, sp_nt, terms, 0); });
-            if (!k.wimg) return 0;
-            if (sp && p.Cout == 256) {
-                q.wimg_h1[n - 1] = weight_image(e, sp_key + "_h1", [&] { return wpack::chunk_sp(w, lo, sp_nt, terms, 128); });
-                if (!q.wimg_h1[n - 1]) return 0;
+                         : weight_image(e, r.nsplit == 2 ? sp_key + "_h0" : sp_key, [&] { return wpack::chunk_sp(w, lo, r.NT, terms, 0); });
+            if (!k.wimg) return false;
+            if (r.nsplit == 2) {      // Cout 256: two N-halves of 128 channels, one image per chunk and half
+                q.wimg_h1[n - 1] = weight_image(e, sp_key + "_h1", [&] { return wpack::chunk_sp(w, lo, r.NT, terms, 128); });
+                if (!q.wimg_h1[n - 1]) return false;
             }
             (sg.taps == 9 ? q.n9 : q.n1) += 1;
         }
@@ -517,18 +531,31 @@ static int attach_pp(Builder& bd, const ConvParams& p, int stride, int up, PPPar
     q.B = p.B; q.H = p.H; q.W = p.W;
     q.out = p.out; q.addvec = p.addvec; q.addvec_bs = p.addvec_bs; q.residual = p.residual; q.res_scale = p.res_scale;
     q.stats_out = p.stats_out; q.out_scale = p.out_scale; q.coef = p.coef; q.coef_stride = p.coef_stride; q.scale = p.scale;
-    return sp ? 2 : 1;
+    return true;
 }
 
-static void push_conv(Builder& bd, const ConvParams& p0, int stride = 1, int up = 0) {
+// decide first (conv_route), then build what the chosen kernel needs; returns the family the launch took.  A launch no kernel can run, or an image that
+// cannot be allocated, fails the plan (bd.ok) with a message
+static ConvFamily push_conv(Builder& bd, const ConvParams& p0, int stride = 1, int up = 0) {
+    pf_engine* e = bd.e;
     ConvParams p = with_coef(bd, p0, bd.plan->ops);
-    Op op{}; op.kind = OP_CONV; op.terms = conv_terms(bd.e);
-    op.use_pp = attach_pp(bd, p, stride, up, op.ppp);
-    op.dma = (!op.use_pp && attach_dma(bd, p, stride, up, bd.plan->ops)) ? 1 : 0;
+    Op op{}; op.kind = OP_CONV;
+    op.route = conv_route(routed_shape(e, p), stride, up, conv_terms(e), route_env());
+    const ConvFamily f = op.route.family;
+    bool built = true;
+    if (op.route.refused) { built = false; e->err = std::string("conv launch refused: ") + op.route.refused; }
+    else if (f == ConvFamily::PP || f == ConvFamily::SP) built = attach_pp(bd, p, op.route, op.ppp);
+    else if (f == ConvFamily::DMA) built = attach_dma(bd, p, op.route, bd.plan->ops);
+    if (!built) {
+        if (bd.ok) { bd.ok = false; if (!op.route.refused) e->err = "conv launch: a weight image or operand buffer could not be allocated"; }
+        return f;
+    }
     op.cp = p; op.stride = stride; op.up = up; op.flops = conv_flops(p);
     bd.plan->gemm_flops += op.flops;
     bd.plan->ops.push_back(op);
+    return f;
 }
+
 
 // ResidualBlock (models.py:94-113).  in1.p != nullptr: input is cat[in0, in1].
 static Tensor res_block(Builder& bd, const ResDesc& r, const Tensor& in0, const Tensor* in1, float* temb_vec) {
@@ -738,16 +765,10 @@ static bool push_conv_up_phase(Builder& bd, const ConvParams& p0, const Tensor& 
     ConvParams q = p0;
     add_seg(q, x, 0, 4, 0);
     ConvSeg& sg = q.seg[0];
-    if (!conv_dma_phase_shape_ok(q, terms)) return false;      // (before any weight image is built)
+    if (!conv_route_phase_ok(route_shape(q), terms, route_env())) return false;      // (before any weight image is built)
     sg.w16 = packed_conv16(e, phase_weight(e, wname), 0, sg.C);
-    if (!sg.w16) return false;
-    ConvParams p = with_coef(bd, q, bd.plan->ops);
-    Op op{}; op.kind = OP_CONV; op.terms = terms;
-    op.dma = attach_dma(bd, p, 1, 2, bd.plan->ops) ? 1 : 0;
-    if (!op.dma) { bd.ok = false; e->err = "phase upsampling conv: conv_dma refused a launch it had accepted"; return false; }
-    op.cp = p; op.stride = 1; op.up = 2; op.flops = conv_flops(p);
-    bd.plan->gemm_flops += op.flops;
-    bd.plan->ops.push_back(op);
+    if (!sg.w16) { bd.ok = false; e->err = "phase upsampling conv: the phase weight image could not be allocated"; return true; }
+    if (push_conv(bd, q, 1, 2) != ConvFamily::DMA && bd.ok) { bd.ok = false; e->err = "phase upsampling conv: conv_dma refused a launch it had accepted"; }
     return true;
 }
 
@@ -771,7 +792,7 @@ static Tensor resample_conv(Builder& bd, const std::string& pfx, const Tensor& x
 static void fix_stats(Op& op, double* slab) {
     auto fx = [&](const double*& p) { if (p) p = (const double*)((char*)slab + ((uintptr_t)p - 1)); };
     auto fxm = [&](double*& p) { if (p) p = (double*)((char*)slab + ((uintptr_t)p - 1)); };
-    if (op.kind == OP_CONV) { for (int i = 0; i < op.cp.nseg; ++i) fx(op.cp.seg[i].stats); fxm(op.cp.stats_out); fxm(op.cp.gnb_sum); if (op.use_pp) op.ppp.stats_out = op.cp.stats_out; }
+    if (op.kind == OP_CONV) { for (int i = 0; i < op.cp.nseg; ++i) fx(op.cp.seg[i].stats); fxm(op.cp.stats_out); fxm(op.cp.gnb_sum); if (op.route.family == ConvFamily::PP || op.route.family == ConvFamily::SP) op.ppp.stats_out = op.cp.stats_out; }
     if (op.kind == OP_GN_COEF) for (int i = 0; i < op.gp.nseg; ++i) fx(op.gp.st[i]);
     if (op.kind == OP_STATS) { double* d = (double*)op.O; fxm(d); op.O = d; }
     if (op.kind == OP_NX_FIR) fxm(op.fp.stats_raw);
@@ -994,7 +1015,10 @@ struct BwdCtx {
         conv_plain(p, stride, up);
     }
     void conv_plain(const ConvParams& p, int stride = 1, int up = 0) {
-        Op op{}; op.kind = OP_CONV; op.terms = conv_terms(e); op.cp = p; op.stride = stride; op.up = up; op.flops = conv_flops(p);
+        Op op{}; op.kind = OP_CONV; op.cp = p; op.stride = stride; op.up = up; op.flops = conv_flops(p);
+        // (no prep pass and no chunk list in the backward: conv_mfma16 where every segment has a 16-bit image, else conv_mfma)
+        op.route = conv_route(route_shape(p), stride, up, conv_terms(e), mfma_only(route_env()));
+        if (op.route.refused && bd->ok) { bd->ok = false; e->err = std::string("backward conv launch refused: ") + op.route.refused; }
         plan->bwd_flops += op.flops;
         push(op);
     }
@@ -1370,15 +1394,14 @@ static int run_backward(pf_engine* e, Plan* plan, const float* vec, float* g, hi
 }
 
 static hipError_t dispatch_conv(const Op& op, hipStream_t s) {
-    if (op.use_pp == 2) return launch_conv_sp(op.ppp, s, op.terms);
-    if (op.use_pp == 1) return launch_conv_pp(op.ppp, s, op.terms);
-    if (op.dma) return launch_conv_dma(op.cp, op.up, s, op.terms);
-    if (op.terms != 0) {
-        bool ok16 = true;
-        for (int i = 0; i < op.cp.nseg; ++i) ok16 &= op.cp.seg[i].w_mode == 0 && op.cp.seg[i].w16 != nullptr;
-        if (ok16) return launch_conv16(op.cp, op.stride, op.up, s, op.terms);
+    switch (op.route.family) {
+        case ConvFamily::SP: return launch_conv_sp(op.ppp, op.route, s);
+        case ConvFamily::PP: return launch_conv_pp(op.ppp, op.route, s);
+        case ConvFamily::DMA: return launch_conv_dma(op.cp, op.route, s);
+        case ConvFamily::MFMA16: return launch_conv16(op.cp, op.route, s);
+        case ConvFamily::MFMA32: return launch_conv(op.cp, op.route, s);
     }
-    return launch_conv(op.cp, op.stride, op.up, s);
+    return hipErrorInvalidValue;
 }
 
 static int run_plan(pf_engine* e, Plan* plan, const float* x, const float* t, float* v, hipStream_t s, float t_scale = 1.0f) {
@@ -2154,7 +2177,7 @@ int pf_engine_profile_read(pf_engine* e, int64_t* launches, double* ms_conv_gemm
             double bytes = (double)op.cp.B * op.cp.H * op.cp.W * op.cp.Cout * 4.0 * (op.cp.residual ? 2.0 : 1.0);
             for (int j = 0; j < op.cp.nseg; ++j) bytes += (double)op.cp.B * op.cp.Hs * op.cp.Ws * op.cp.seg[j].C * 4.0;
             fprintf(dump, "%zu,%d,%d,%d,%zu,%d,%d,%d,%d,%.4f,%.2f,%.2f,%d,%.3f", i, op.cp.H, op.cp.W, op.cp.Cout, K, op.cp.nseg, op.cp.seg[0].taps,
-                    op.stride, op.up, op.flops / 1e9, ms * 1e3, op.flops / (ms * 1e-3) / 1e12, op.use_pp == 2 ? 5 : op.use_pp ? 2 : op.dma, bytes / 1e6);
+                    op.stride, op.up, op.flops / 1e9, ms * 1e3, op.flops / (ms * 1e-3) / 1e12, op.route.csv_code, bytes / 1e6);
             fprintf(dump, "\n");
         }
     }

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <atomic>
 
+#include "conv_route.h"
 #include "deg_rules.h"
 
 namespace pf {
@@ -98,7 +99,7 @@ struct ConvParams {
     const float* gnb_gamma; const float* gnb_beta;    // [gnb_Ct]
     int gnb_Ct, gnb_coff, gnb_silu;
     double* gnb_sum;             // [B][gnb_Ct][2] += (sum dyhat, sum dyhat*yhat)
-    int xcd_map;          // split-fp16 kernel, set by its launcher: 1 = workgroup -> (tile, N-block) mapping that keeps neighbouring tiles and the N-blocks of a tile on one XCD
+    int xcd_map;          // split-fp16 kernels, set by their launchers from ConvRoute::xcd_map: 1 = workgroup -> (tile, N-block) mapping that keeps neighbouring tiles and the N-blocks of a tile on one XCD
     // round 6 (split-fp16 kernels): output channels >= pack_from_p1 - 1 (a multiple of 4; 0 = none) leave as PACKED fp16 pairs - per element the 32-bit word
     // hi | lo << 16 with hi = RNE16(v), lo = RNE16(v - hi), the split the fused attention core applies to its keys and values - in place of the fp32 value: the
     // stacked q,k,v conv packs its k and v channels, so the core's 32 query tiles per image unpack (two v_perm per pair) instead of each converting every key and value
@@ -110,6 +111,19 @@ struct ConvParams {
     // out_cstride = 2 C, dst_row_pitch = 2 W' the launch writes output phase (py, px) of a tensor twice as large (the stride-2 conv's adjoint, engine.hip)
     int dst_row_pitch;
 };
+
+// what conv_route() may know of a launch (the engine adds the weight-source facts of its segments, which live in its own tables)
+inline RouteShape route_shape(const ConvParams& p) {
+    RouteShape r;
+    r.nseg = p.nseg; r.B = p.B; r.H = p.H; r.W = p.W; r.Hs = p.Hs; r.Ws = p.Ws; r.Cout = p.Cout;
+    r.out_cstride = p.out_cstride; r.res_cstride = p.res_cstride; r.gn_C = p.gn_C;
+    r.residual = p.residual != nullptr; r.addvec = p.addvec != nullptr; r.coef = p.coef != nullptr; r.scale = p.scale != nullptr; r.gnb = p.gnb_x != nullptr;
+    for (int i = 0; i < p.nseg && i < 3; ++i) {
+        const ConvSeg& s = p.seg[i]; RouteSeg& q = r.seg[i];
+        q.C = s.C; q.cstride = s.cstride; q.taps = s.taps; q.xform = s.xform; q.w_mode = s.w_mode; q.has_w16 = s.w16 != nullptr;
+    }
+    return r;
+}
 
 // fp32 -> packed (hi | lo << 16) fp16 pair, the exact split of attention.hip's split4 (the value is made opaque first: see the note there)
 #if defined(__HIPCC__)
@@ -188,15 +202,12 @@ struct PrepParams {
     const float* scale;                      // ConvParams::scale, or nullptr
 };
 hipError_t launch_prep_split(const PrepParams& p, hipStream_t s);
-bool conv_dma_supported(const ConvParams& p, int stride, int up, int terms);
-bool conv_dma_phase_shape_ok(const ConvParams& p, int terms);      // the nearest-x2 upsampling conv described by p (its 9-tap form) can run in conv_dma's phase form (up = 2)
-hipError_t launch_conv_dma(const ConvParams& p, int up, hipStream_t s, int terms);
+hipError_t launch_conv_dma(const ConvParams& p, const ConvRoute& r, hipStream_t s);
 size_t conv_dma_a16_bytes(int B, int C, int Hs, int Ws, int terms);
 
 // conv_pp.hip: persistent two-team kernel of the full-resolution 32-channel level.  A launch is a list of 32-channel K-chunks (9-tap chunks
 // with GroupNorm(+SiLU) staging first, then raw 1-tap chunks of a folded 1x1 shortcut), each with its own LDS weight image
 // (layouts in weight_pack.h: wpack::chunk_pp; wpack::chunk_sp for the 16-channel chunks of conv_sp.hip).
-constexpr int PP_MAXCH = 32;     // conv_pp: <= 4 chunks of 32 channels; conv_sp: <= 32 chunks of 16 channels (cat[256, 256] -> 256)
 struct PPChunk {
     const float* src;     // NHWC source tensor of the chunk's K-segment
     const void* wimg;     // weight image of this chunk in global memory: taps * 4 KiB (conv_sp: 36 / 72 KiB per 16-channel chunk of 64 / 128 output channels)
@@ -216,13 +227,12 @@ struct PPParams {
     const float* coef; int coef_stride; const float* scale;      // ConvParams::coef / ::scale of the launch
     const void* wimg_h1[PP_MAXCH];        // conv_sp at cout 256 only: per chunk, the weight image of output channels 128-255 (ch[c].wimg: channels 0-127)
 };
-bool conv_pp_supported(const ConvParams& p, int stride, int up, int terms);
-hipError_t launch_conv_pp(const PPParams& p, hipStream_t s, int terms = 3);      // terms 1: precision mode 2 (hi-only operands)
-bool conv_sp_supported(const ConvParams& p, int stride, int up, int terms);      // conv_sp.hip: one wave per SIMD, software-pipelined (Cout = 64 / 128, 256 as two halves)
-hipError_t launch_conv_sp(const PPParams& p, hipStream_t s, int terms = 3);      // terms 1: precision mode 2 (hi-only operands and weight images)
-
-hipError_t launch_conv(const ConvParams& p, int stride, int up, hipStream_t s);
-hipError_t launch_conv16(const ConvParams& p, int stride, int up, hipStream_t s, int terms = 3);   // split-fp16 MFMA variant (terms 3) / single fp16 MFMA (terms 1)
+// Every conv launcher takes the ConvRoute the engine got from conv_route() (conv_route.h) at plan build and switches on its instantiation fields; a route
+// its file does not instantiate is hipErrorInvalidValue.  r.terms 1: precision mode 2 (hi-only operands and weight images)
+hipError_t launch_conv_pp(const PPParams& p, const ConvRoute& r, hipStream_t s);
+hipError_t launch_conv_sp(const PPParams& p, const ConvRoute& r, hipStream_t s);      // conv_sp.hip: one wave per SIMD, software-pipelined (Cout = 64 / 128, 256 as two halves)
+hipError_t launch_conv(const ConvParams& p, const ConvRoute& r, hipStream_t s);
+hipError_t launch_conv16(const ConvParams& p, const ConvRoute& r, hipStream_t s);     // split-fp16 MFMA variant (terms 3) / single fp16 MFMA (terms 1)
 size_t conv_flops(const ConvParams& p);
 hipError_t launch_begin_conv(const EdgeConvParams& p, hipStream_t s);
 hipError_t launch_end_conv(const EdgeConvParams& p, hipStream_t s);
