@@ -260,6 +260,17 @@ int pf_fused_bias_act(const float* x, const float* bias, const float* ref, float
  * Shapes: T in {128, 256, 512, 768, ... 4096}, C in {128, 256}; anything else returns PF_ERR_INVALID (the engine then
  * uses three launches). */
 int pf_attention_core(const float* qkv, float* out, int B, int T, int C, void* stream);
+/* The same core with every option of the engine's launch (additive: PF_ABI_VERSION unchanged):
+ *   kv_packed != 0   the k and v thirds of qkv hold, per element, the 32-bit word hi | lo << 16 of two fp16 values,
+ *                    hi = RNE16(x), lo = RNE16(x - hi), in place of the fp32 value (q stays fp32);
+ *   residual[B,T,C]  the folded output projection: out = (P v + bias[c]) + residual (bias[C] may be NULL = 0);
+ *   stats_part       fp32 scratch [B][T/32][C][2] and stats double [B][C][2]: per image and channel the (sum, sum of
+ *                    squares) of out over the tokens, 32-token tiles in fp32, tiles added in order in fp64 (deterministic).
+ * Operand contract: finite results need |q|, |k|, |v| <= 65504; the error is 2e-5 max|P v| + 2^-24 absolute.
+ * PF_ERR_INVALID with nothing launched for: the shapes pf_attention_core refuses, NULL qkv / out, B <= 0, bias or
+ * stats_part without residual, one of stats_part / stats without the other, out == residual. */
+int pf_attention_core_ex(const float* qkv, float* out, int B, int T, int C, const float* bias, const float* residual, float* stats_part, double* stats,
+                         int kv_packed, void* stream);
 
 /* ---- vector-Jacobian product (OT-ODE) ------------------------------------------------ */
 /* replaces torch.autograd.functional.vjp(lambda z: model(z, t), x, vec) at

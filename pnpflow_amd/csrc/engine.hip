@@ -1787,6 +1787,20 @@ int pf_attention_core(const float* qkv, float* out, int B, int T, int C, void* s
     LAUNCHCHK(launch_attn_fused(ap, (hipStream_t)stream));
     return PF_OK;
 }
+// every field of AttnParams from the caller (the packed keys / values and the folded epilogue of attention.hip), for tests and integrators.  attn_store
+// reads bias and stats_part only on its residual branch, so either without a residual would be dropped silently: refused.  out == residual is refused too:
+// the engine never aliases them, so nothing pins that each element is read and written by the same lane only.
+int pf_attention_core_ex(const float* qkv, float* out, int B, int T, int C, const float* bias, const float* residual, float* stats_part, double* stats,
+                         int kv_packed, void* stream) {
+    if (!qkv || !out || B <= 0 || !attn_fused_supported(T, C)) return PF_ERR_INVALID;
+    if (!residual && (bias || stats_part)) return PF_ERR_INVALID;
+    if ((stats_part == nullptr) != (stats == nullptr)) return PF_ERR_INVALID;
+    if (residual == out) return PF_ERR_INVALID;
+    AttnParams ap{qkv, out, B, T, C, 1.0f / sqrtf((float)C), bias, residual, stats_part, kv_packed ? 1 : 0};
+    LAUNCHCHK(launch_attn_fused(ap, (hipStream_t)stream));
+    if (stats_part) LAUNCHCHK(launch_partial_stats(stats_part, stats, B, T / 32, C, (hipStream_t)stream));
+    return PF_OK;
+}
 
 int pf_psnr(const float* rec, const float* clean, float* out, int B, int n_per_image, void* stream) {
     if (!rec || !clean || !out) return PF_ERR_INVALID;
