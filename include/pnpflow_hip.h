@@ -241,6 +241,48 @@ int pf_lpips_load_weight(pf_lpips* l, const char* name, const float* host_data, 
  * package's 2x - 1 first (the reference passes normalize=True on images that already are in [-1, 1]: utils.py:703-708). */
 int pf_lpips_forward(pf_lpips* l, const float* img0, const float* img1, float* out, int B, int H, int W, int normalize, void* stream);
 
+/* ---- FID Inception features (additive: PF_ABI_VERSION unchanged) ----------------------------------------------------------------
+ * The feature network of the reference's FID (pnpflow/models.py:498-820: InceptionV3 on pytorch-fid's fid_inception_v3, eval mode),
+ * restated in csrc/inception.hip from the layer table of csrc/inception_plan.h.  PARITY UNPINNED for the network: torchvision and the
+ * published weight file are not in the build image.  The statistics and the Frechet distance on top live in pnpflow_amd/fid_score.py. */
+typedef struct pf_inception pf_inception;
+int pf_inception_create(int device_id, pf_inception** out);
+void pf_inception_destroy(pf_inception* h);
+const char* pf_inception_last_error(const pf_inception* h);
+/* The layer table (host only, no device needed): layer `index` of pf_inception_num_layers, its name and
+ * dims[7] = (Cin, Cout, KH, KW, stride, pad_h, pad_w). */
+int pf_inception_num_layers(void);
+int pf_inception_layer(int index, char* name, int name_cap, int32_t* dims);
+/* The published state_dict names (models.py:694-695 loads them): "<layer>.conv.weight" [Cout][Cin][KH][KW] and
+ * "<layer>.bn.{weight,bias,running_mean,running_var}" [Cout], <layer> e.g. "Conv2d_1a_3x3" or "Mixed_6c.branch7x7dbl_3".  The conv
+ * weights are repacked and the BatchNorm (eps 1e-3) is folded into a scale and a shift here, once.  Unknown name / wrong shape:
+ * PF_ERR_WEIGHTS. */
+int pf_inception_load_weight(pf_inception* h, const char* name, const float* host_data, const int64_t* shape, int ndim);
+/* InceptionV3.forward (models.py:617-651) followed by the spatial average of fid_score.py:60-65: img [B][3][H][W] fp32 on the device,
+ * values in (0, 1) when normalize_input; out [B][dims] on the device, dims = 64 / 192 / 768 / 2048 for output_block 0..3.
+ * resize_input: bilinear to 299 x 299 (align_corners=False).  Without it a side below 75 is refused with PF_ERR_INVALID and a message
+ * (nothing is launched); a missing weight is PF_ERR_STATE.  Activation buffers are planned per (B, H, W) and regrown when a call needs
+ * more.  Asynchronous on `stream`. */
+int pf_inception_forward(pf_inception* h, const float* img, float* out, int B, int H, int W, int resize_input, int normalize_input, int output_block,
+                         void* stream);
+/* HIP-event time of every launch of the following forwards (they then synchronise `stream`); read back launch `index` of the last one
+ * (PF_ERR_INVALID past the end): its layer name (or "front", "maxpool", "avgpool", "global_average"), milliseconds and
+ * floating-point operations (2 M K Cout of a conv, 0 otherwise). */
+int pf_inception_profile(pf_inception* h, int enable);
+int pf_inception_profile_read(pf_inception* h, int index, char* name, int name_cap, float* ms, double* flops);
+/* One launch of the network's conv kernel, for tests (one BasicConv2d of models.py:498-820 with the BatchNorm already folded):
+ * in NHWC [B][Hi][Wi][Cin] (device), host_weight [Cout][Cin][KH][KW] (HOST; packed and uploaded here), scale / shift [Cout] (device),
+ * out NHWC [B][Ho][Wo][out_cs] (device): channels [out_off, out_off + Cout) <- relu(conv * scale + shift), the others untouched.
+ * tile: 0 128x128, 1 128x64, 2 64x128, 3 64x64 (pixels x channels per workgroup), negative: the planner's choice.  Cout % 4 == 0.
+ * Synchronises `stream`. */
+int pf_inception_conv(const float* in, const float* host_weight, const float* scale, const float* shift, float* out, int B, int Hi, int Wi, int Cin, int Cout,
+                      int KH, int KW, int stride, int pad_h, int pad_w, int out_off, int out_cs, int tile, void* stream);
+/* The network's 3 x 3 pools on channel slices of NHWC tensors (device), for tests.  kind 1: max, stride 2, no pad; 2: average, stride 1,
+ * pad 1, count_include_pad=False (models.py:715-718); 3: max, stride 1, pad 1 (models.py:812-816). */
+int pf_inception_pool(const float* in, float* out, int B, int C, int Hi, int Wi, int kind, int in_off, int in_cs, int out_off, int out_cs, void* stream);
+/* The front end (models.py:634-641), for tests: img NCHW [B][3][H][W] -> out NHWC [B][299 | H][299 | W][3]. */
+int pf_inception_front(const float* img, float* out, int B, int H, int W, int resize_input, int normalize_input, void* stream);
+
 /* ---- the reference's native ops (NCSN++ "rectified" velocity net) ------------------------------------------- */
 /* upfirdn2d (pnpflow/image_generation/op/upfirdn2d_kernel.cu:49-369; definition: op/upfirdn2d.py:142-187): per plane of
  * in[planes][in_h][in_w]: zero-insert upsample by (up_x, up_y), pad (negative = crop) by (pad_x0, pad_x1, pad_y0, pad_y1), true 2-D

@@ -10,6 +10,9 @@ pnpflow_amd/dataloaders.py) is missing; `--opts synthetic True` is the explicit 
 seed-fixed synthetic weights / images (smoke runs without the downloads) and writes under
 `results_synthetic*/` so that such numbers can never mix with real ones.
 
+`compute_metrics True` first computes the FID of `fid_samples` (default 5000) prior samples against as many test images
+(pnpflow_amd/compute_metric.py; reference main.py:112-118) at `fid_dims` Inception features (2048, or 64 / 192 / 768), then restores.
+
 Multi-GPU: `torchrun --nproc-per-node N main.py --opts ...` - one process per GPU, every
 rank restores its contiguous slice of each test batch, one all_gather of per-image metrics
 per logging point, rank 0 writes the reference's result files (pnpflow_amd/parallel.py).
@@ -98,6 +101,35 @@ class SyntheticLoader:
             yield ((x - lo) / (hi - lo) * 2 - 1).contiguous(), torch.zeros(self.bs)
 
 
+def compute_fid_metric(args, model, model_path, device, world, synthetic):
+    """`compute_metrics True` (reference main.py:112-118): FID of `fid_samples` prior samples against one test batch of as many images."""
+    from pnpflow_amd.compute_metric import ComputeMetric
+    from pnpflow_amd.dataloaders import DataLoaders
+    from pnpflow_amd.models import InceptionV3, find_fid_weights
+    from pnpflow_amd.train_flow_matching import FLOW_MATCHING
+    if world > 1:
+        raise SystemExit("compute_metrics runs on one GPU (the FID's sampling and statistics are not distributed): start it without torchrun")
+    if args.model not in ("ot", "indep"):
+        raise SystemExit(f"compute_metrics samples the flow prior through FLOW_MATCHING, which takes model 'ot' or 'indep', not {args.model!r}")
+    n, dims = int(getattr(args, "fid_samples", 5000)), int(getattr(args, "fid_dims", 2048))
+    if dims not in InceptionV3.BLOCK_INDEX_BY_DIM:
+        raise SystemExit(f"fid_dims must be one of {sorted(InceptionV3.BLOCK_INDEX_BY_DIM)}, not {dims}")
+    args.fid_dims = dims
+    print('Computing metrics...')
+    dl = DataLoaders(args.dataset, n, n, root=args.root)
+    if dl.available('test'):
+        data_loaders, data_synthetic = dl.load_data(), False
+    elif synthetic:
+        print(f"[pnpflow_amd] synthetic=True: dataset files {dl.paths()} not found, using SYNTHETIC test images for the FID")
+        data_loaders, data_synthetic = {'test': SyntheticLoader(n, args.num_channels, args.dim_image, 1)}, True
+    else:
+        raise FileNotFoundError(f"dataset files {dl.paths()} not found. Pass `--opts synthetic True` to run on synthetic images instead.")
+    real = not data_synthetic and os.path.isfile(model_path) and find_fid_weights(args.output_root) is not None
+    metric = ComputeMetric(data_loaders, FLOW_MATCHING(model, device, args), device, args, results_dir='results' if real else 'results_synthetic')
+    fid = metric.compute_metrics(n)
+    print(f'Computing metrics done! FID ({n} samples, {dims} features): {fid} -> {metric.save_path}metrics.txt')
+
+
 def main():
     args = parse_args()
     if args.method == 'pnp_gs' and args.model != 'gradient_step':
@@ -131,6 +163,8 @@ def main():
             raise FileNotFoundError(f"{model_path} not found (the reference's checkpoint, download.sh). "
                                     "Pass `--opts synthetic True` to run on seed-fixed synthetic weights instead.")
         model.eval()
+        if getattr(args, "compute_metrics", False):
+            compute_fid_metric(args, model, model_path, device, world, synthetic)
         degradation, sigma_noise = make_degradation(args.problem, args.dim_image, args.num_channels, args.noise_type, device, psf=getattr(args, "psf", "motion"),
                                                     psf_size=getattr(args, "psf_size", None), psf_seed=getattr(args, "psf_seed", 0), sf=getattr(args, "sf", None))
         if rank == 0:

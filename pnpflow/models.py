@@ -1,1 +1,1 @@
-from pnpflow_amd.models import UNet  # noqa: F401
+from pnpflow_amd.models import InceptionV3, UNet  # noqa: F401

@@ -132,6 +132,18 @@ SIGNATURES = {
     "pf_lpips_last_error": (C.c_char_p, [C.c_void_p]),
     "pf_lpips_load_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
     "pf_lpips_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "pf_inception_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    "pf_inception_destroy": (None, [C.c_void_p]),
+    "pf_inception_last_error": (C.c_char_p, [C.c_void_p]),
+    "pf_inception_load_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    "pf_inception_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "pf_inception_num_layers": (C.c_int, []),
+    "pf_inception_layer": (C.c_int, [C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32)]),
+    "pf_inception_profile": (C.c_int, [C.c_void_p, C.c_int]),
+    "pf_inception_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
+    "pf_inception_conv": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 13 + [C.c_void_p]),
+    "pf_inception_pool": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 9 + [C.c_void_p]),
+    "pf_inception_front": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
     "pf_ot_ode_restore": (C.c_int, [C.c_void_p, C.POINTER(PfDegradation), C.POINTER(PfOtOdeParams), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, ITER_CB, C.c_void_p]),
     "pf_ot_ode_krylov_iterations": (C.c_int64, [C.c_void_p]),
     "pf_krylov_workspace_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -231,3 +231,171 @@ class UNet(_EngineNet):
         self._h = h
         self._loaded = False
         self.training = False
+
+
+FID_WEIGHTS_FILE = "pt_inception-2015-12-05-6726825d.pth"      # pytorch-fid's port of the TensorFlow FID Inception weights (reference models.py:501)
+
+
+def find_fid_weights(output_root=None):
+    """Path of the FID Inception weight file, or None: $PNPFLOW_FID_WEIGHTS (the file, or a folder holding it), <output_root>model/, then
+    torch.hub's checkpoint folder, where the reference's load_state_dict_from_url leaves it (models.py:694)."""
+    import os
+    cands = []
+    env = os.environ.get("PNPFLOW_FID_WEIGHTS")
+    if env:
+        cands += [env, os.path.join(env, FID_WEIGHTS_FILE)]
+    if output_root is not None:
+        cands.append(os.path.join(str(output_root) + "model", FID_WEIGHTS_FILE))
+    cands.append(os.path.join(os.path.expanduser("~/.cache/torch/hub/checkpoints"), FID_WEIGHTS_FILE))
+    return next((p for p in cands if os.path.isfile(p)), None)
+
+
+class InceptionV3:
+    """The FID feature network with the surface of the reference's InceptionV3 (pnpflow/models.py:504-651, use_fid_inception=True, eval mode)
+    on csrc/inception.hip.
+
+        net = InceptionV3([InceptionV3.BLOCK_INDEX_BY_DIM[2048]]); net.load_state_dict(torch.load(find_fid_weights()))
+        pred = net(batch)[0]          # batch: (B, 3, H, W) on the GPU, values in (0, 1)
+
+    `forward` returns one tensor per requested block, ascending, like the reference's - but every block arrives spatially averaged,
+    (B, dims, 1, 1): what fid_score.get_activations takes of it next (fid_score.py:60-65) and what block 3 is anyway.  One engine pass
+    per requested block.  The constructor loads no weights (the reference downloads them there): load_state_dict takes pytorch-fid's
+    key names `<layer>.conv.weight`, `<layer>.bn.{weight,bias,running_mean,running_var}`, ignores `fc.*`, `AuxLogits.*` and
+    `num_batches_tracked`, and raises KeyError naming what is missing.  PARITY UNPINNED: torchvision is absent from the build image.
+    """
+    DEFAULT_BLOCK_INDEX = 3
+    BLOCK_INDEX_BY_DIM = {64: 0, 192: 1, 768: 2, 2048: 3}
+
+    def __init__(self, output_blocks=(DEFAULT_BLOCK_INDEX,), resize_input=True, normalize_input=True, requires_grad=False, use_fid_inception=True,
+                 device_index: int = 0):
+        if requires_grad or not use_fid_inception:
+            raise NotImplementedError("the engine runs the FID Inception network in inference (use_fid_inception=True, requires_grad=False)")
+        self.output_blocks = sorted(int(b) for b in output_blocks)
+        if not self.output_blocks or self.output_blocks[0] < 0 or self.output_blocks[-1] > 3:
+            raise ValueError("output blocks are 0..3 (the last possible output block index is 3)")
+        self.last_needed_block = self.output_blocks[-1]
+        self.resize_input, self.normalize_input = bool(resize_input), bool(normalize_input)
+        self._lib = _lib.load()
+        h = C.c_void_p()
+        _lib.check(self._lib.pf_inception_create(device_index, C.byref(h)), None, "pf_inception_create")
+        self._h = h
+        self._loaded = False
+        self.training = False
+
+    @staticmethod
+    def layer_table():
+        """[(name, Cin, Cout, KH, KW, stride, pad_h, pad_w)] of the 94 convs, as the engine's planner holds them (csrc/inception_plan.h)."""
+        lib = _lib.load()
+        out = []
+        for i in range(lib.pf_inception_num_layers()):
+            name, dims = C.create_string_buffer(96), (C.c_int32 * 7)()
+            _lib.check(lib.pf_inception_layer(i, name, 96, dims), None, "pf_inception_layer")
+            out.append((name.value.decode(),) + tuple(int(d) for d in dims))
+        return out
+
+    @classmethod
+    def state_dict_shapes(cls):
+        """{published key: shape} of everything load_state_dict needs."""
+        out = {}
+        for (n, ci, co, kh, kw, _s, _ph, _pw) in cls.layer_table():
+            out[n + ".conv.weight"] = (co, ci, kh, kw)
+            for s in ("weight", "bias", "running_mean", "running_var"):
+                out[f"{n}.bn.{s}"] = (co,)
+        return out
+
+    def _err(self):
+        return (self._lib.pf_inception_last_error(self._h) or b"").decode()
+
+    @classmethod
+    def select_weights(cls, state_dict, strict: bool = True):
+        """{published key: tensor} of exactly what the network needs, out of a pytorch-fid state_dict: `fc.*`, `AuxLogits.*` and
+        `*.num_batches_tracked` are ignored, a missing key is a KeyError that names it, any other extra key is one too when strict."""
+        sd = {(k[7:] if k.startswith("module.") else k): v for k, v in state_dict.items()}
+        need = cls.state_dict_shapes()
+        missing = [k for k in need if k not in sd]
+        if missing:
+            raise KeyError(f"FID Inception weights missing: {missing[:8]}{' ...' if len(missing) > 8 else ''} ({len(missing)} of {len(need)} keys)")
+        unexpected = [k for k in sd if k not in need and not k.startswith(("fc.", "AuxLogits.")) and not k.endswith("num_batches_tracked")]
+        if strict and unexpected:
+            raise KeyError(f"unexpected keys for the FID Inception network: {unexpected[:8]}")
+        for k, shape in need.items():
+            if tuple(sd[k].shape) != tuple(shape):
+                raise ValueError(f"FID Inception weight {k} has shape {tuple(sd[k].shape)}, expected {tuple(shape)}")
+        return {k: sd[k] for k in need}
+
+    def load_state_dict(self, state_dict, strict: bool = True):
+        sd = need = self.select_weights(state_dict, strict)
+        for k in need:
+            a = np.ascontiguousarray(sd[k].detach().cpu().to(torch.float32).numpy())
+            shp = (C.c_int64 * a.ndim)(*a.shape)
+            rc = self._lib.pf_inception_load_weight(self._h, k.encode(), a.ctypes.data_as(C.c_void_p), shp, a.ndim)
+            if rc != 0:
+                raise _lib.PnpFlowHipError(f"pf_inception_load_weight({k}) failed (status {rc}): {self._err()}")
+        self._loaded = True
+        return self
+
+    def to(self, device=None):
+        return self
+
+    def eval(self):
+        return self
+
+    def parameters(self):
+        return iter(())
+
+    def profile(self, enable: bool):
+        _lib.check(self._lib.pf_inception_profile(self._h, 1 if enable else 0), None, "pf_inception_profile")
+
+    def profile_read(self):
+        """[(launch name, milliseconds, floating-point operations)] of the last profiled forward."""
+        out, i = [], 0
+        name, ms, fl = C.create_string_buffer(96), C.c_float(), C.c_double()
+        while self._lib.pf_inception_profile_read(self._h, i, name, 96, C.byref(ms), C.byref(fl)) == 0:
+            out.append((name.value.decode(), float(ms.value), float(fl.value))); i += 1
+        return out
+
+    def features(self, inp: torch.Tensor, block: int) -> torch.Tensor:
+        """(B, dims) spatially averaged output of one block."""
+        if not inp.is_cuda:
+            raise _lib.PnpFlowHipError("InceptionV3 needs GPU tensors (there is no CPU path)")
+        if inp.ndim != 4 or inp.shape[1] != 3:
+            raise ValueError(f"InceptionV3 expects (B, 3, H, W) images, got {tuple(inp.shape)}")
+        x = inp.detach().contiguous().float()
+        B, _c, H, W = x.shape
+        dims = {v: k for k, v in self.BLOCK_INDEX_BY_DIM.items()}[int(block)]
+        out = torch.empty((B, dims), dtype=torch.float32, device=x.device)
+        if B == 0:
+            return out
+        rc = self._lib.pf_inception_forward(self._h, x.data_ptr(), out.data_ptr(), B, H, W, int(self.resize_input), int(self.normalize_input), int(block),
+                                            _lib.current_stream_ptr())
+        if rc != 0:
+            raise _lib.PnpFlowHipError(f"pf_inception_forward failed (status {rc}): {self._err()}")
+        return out
+
+    def forward(self, inp: torch.Tensor):
+        return [self.features(inp, b)[:, :, None, None] for b in self.output_blocks]
+
+    __call__ = forward
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self._lib.pf_inception_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+def load_fid_inception(output_blocks=(3,), output_root=None, synthetic=False, device_index=0, resize_input=True, normalize_input=True):
+    """(InceptionV3 with weights, real) - the published weights when find_fid_weights has them; otherwise FileNotFoundError, unless
+    `synthetic` opts into seed-fixed synthetic weights (tools/synthetic_inception.py; the FID is then not comparable with anything)."""
+    net = InceptionV3(output_blocks, resize_input=resize_input, normalize_input=normalize_input, device_index=device_index)
+    path = find_fid_weights(output_root)
+    if path is not None:
+        return net.load_state_dict(torch.load(path, map_location="cpu")), True
+    if not synthetic:
+        raise FileNotFoundError(f"{FID_WEIGHTS_FILE} not found in $PNPFLOW_FID_WEIGHTS, <output_root>model/ or ~/.cache/torch/hub/checkpoints/ (pytorch-fid's "
+                                "release 'fid_weights'). Pass `--opts synthetic True` to run on seed-fixed synthetic weights instead.")
+    print(f"[pnpflow_amd] synthetic=True: {FID_WEIGHTS_FILE} not found, using SYNTHETIC Inception weights (the FID is not meaningful)")
+    from tools.synthetic_inception import synthetic_inception_state_dict
+    return net.load_state_dict(synthetic_inception_state_dict(InceptionV3.state_dict_shapes())), False

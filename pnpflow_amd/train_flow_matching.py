@@ -6,7 +6,7 @@
 
 The reference hands `cnf(model)` to torchdiffeq; here the adaptive solve is pf_flow_ode_dopri5 (torchdiffeq's dopri5 rules) and the
 fixed-grid one pf_flow_ode_euler, both on the device.  The latents are torch.randn draws on the device, as in the reference, or injected.
-Training the flow and the FID evaluation are out of scope.
+Training the flow is out of scope; compute_fid runs on the engine's Inception network (models.InceptionV3).
 """
 from __future__ import annotations
 
@@ -97,7 +97,7 @@ class FLOW_MATCHING(object):
                 images_list.append(self._dopri5(x0, float(time_points[0]), float(time_points[-1]), tol))
         return torch.cat(images_list, dim=0)
 
-    # ---- training / FID: out of scope of this engine -------------------------------------------------------------------------------
+    # ---- training: out of scope of this engine; FID -------------------------------------------------------------------------------
     def train_FM_model(self, train_loader, opt, num_epoch):
         raise NotImplementedError("training the flow-matching model is not implemented by this engine (inference only)")
 
@@ -108,4 +108,31 @@ class FLOW_MATCHING(object):
         raise NotImplementedError("sample_plot belongs to the training loop, which is not implemented by this engine; tools/prior_report.py writes a sample grid")
 
     def compute_fid(self, num_images_fid, train_feat, ft_extractor, batch_size=512, integration_method="dopri5", integration_steps=100, epoch='final'):
-        raise NotImplementedError("FID needs the Inception feature extractor, which is not part of this engine; generate_samples gives the images")
+        """FID of num_images_fid samples (generate_samples at tol 1e-4, train_flow_matching.py:200-214) against `train_feat`, the (N, dims)
+        features of the training images from the same `ft_extractor`, a pnpflow_amd.models.InceptionV3.  The reference's goes through the
+        `fld` package (absent): its extractor takes uint8 images; here the PREPROCESSING IS PYTORCH-FID'S - samples mapped from [-1, 1] to
+        [0, 1] and clipped, resized to 299 x 299 and normalised by the network - and the distance is fid_score.calculate_frechet_distance.
+        The grid of the first 16 samples goes to training_images/<dataset>/gen_images_epoch<epoch>.png as in the reference."""
+        import os
+
+        import numpy as np
+
+        from .models import InceptionV3
+        if not isinstance(ft_extractor, InceptionV3) or train_feat is None:
+            raise NotImplementedError("compute_fid takes a pnpflow_amd.models.InceptionV3 as ft_extractor and its (N, dims) features of the training images as "
+                                      "train_feat; the reference's `fld` feature extractors are not implemented by this engine")
+
+        from . import fid_score as fs
+        from . import utils
+        gen_images = self.generate_samples(integration_method=integration_method, tol=1e-4, n_samples=num_images_fid, batch_size=batch_size,
+                                           num_channels=self.num_channels, integration_steps=integration_steps)
+        imgs = (gen_images * 0.5 + 0.5).clip(0, 1)
+        if imgs.shape[1] == 1:
+            imgs = imgs.expand(-1, 3, -1, -1)
+        train_feat = np.asarray(train_feat.cpu() if torch.is_tensor(train_feat) else train_feat, dtype=np.float64)
+        gen_feat = fs.get_activations(imgs, ft_extractor, min(50, len(imgs)), train_feat.shape[1], self.device)
+        fid_val = fs.calculate_frechet_distance(np.mean(train_feat, axis=0), np.cov(train_feat, rowvar=False), np.mean(gen_feat, axis=0), np.cov(gen_feat, rowvar=False))
+        os.makedirs(f"training_images/{self.args.dataset}", exist_ok=True)
+        grid = imgs[:16].permute(0, 2, 3, 1).cpu().numpy()
+        utils._imshow_grid(f"training_images/{self.args.dataset}/gen_images_epoch{epoch}.png", grid, gray=self.num_channels == 1)
+        return fid_val

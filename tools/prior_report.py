@@ -1,6 +1,6 @@
 """Look at a flow-prior checkpoint: a grid of samples drawn from it and a bits/dim table of images under it.
 
-    python tools/prior_report.py --opts dataset celeba model ot [n_samples 16] [integration_method dopri5] [integration_steps 100] [seed 0]
+    python tools/prior_report.py --opts dataset celeba model ot [n_samples 16] [integration_method dopri5] [integration_steps 100] [seed 0] [fid N] [fid_dims 2048]
 
 Uses main.py's config surface (config/main_config.yaml, the dataset YAML, then --opts) to build the net and to find the checkpoint
 `<output_root>model/<dataset>/<model>/model_final.pt` and the test images.  Like main.py it FAILS when either is missing, unless
@@ -9,6 +9,8 @@ Uses main.py's config surface (config/main_config.yaml, the dataset YAML, then -
 Writes `<output_root>results[_synthetic]/<dataset>/<model>/prior_report/`:
     samples.png      n_samples draws (FLOW_MATCHING.generate_samples), postprocessed to [0, 1]
     bits_per_dim.txt one row per image: bits/dim, delta_logp, accepted / rejected steps and evaluations of its batch (get_likelihood_fn_rf)
+    fid.txt          with `fid N`: the FID of N prior samples against N test images (compute_metric.ComputeMetric at fid_dims features; its own
+                     `Epoch: final, FID:` line goes to results[_synthetic]/<dataset>/metrics.txt as main.py's does)
 """
 import argparse
 import os
@@ -28,7 +30,7 @@ def parse_args():
     parser.add_argument('--opts', default=None, nargs=argparse.REMAINDER)
     a = parser.parse_args()
     cfg = load_cfg_from_cfg_file(os.path.join(ROOT, 'config', 'main_config.yaml'))
-    extra = dict(n_samples=16, integration_method="dopri5", integration_steps=100, tol=1e-5, n_images=None)
+    extra = dict(n_samples=16, integration_method="dopri5", integration_steps=100, tol=1e-5, n_images=None, fid=0, fid_dims=2048)
     opts = list(a.opts or [])
     for k in list(extra):          # report-only options: taken out of --opts before the config merge (which knows main.py's keys only)
         if k in opts:
@@ -102,6 +104,23 @@ def main():
         for i, (b, d) in enumerate(zip(bpd.cpu().numpy(), dlp)):
             f.write(f"{i} {b:.6f} {d:.4f}\n")
         f.write(f"# mean {float(bpd.mean()):.6f}\n")
+    if args.fid:
+        from pnpflow_amd.compute_metric import ComputeMetric
+        from pnpflow_amd.models import find_fid_weights
+        fdl = DataLoaders(args.dataset, args.fid, args.fid, root=args.root)
+        if fdl.available('test'):
+            fid_loaders, fid_real = fdl.load_data(), real
+        elif synthetic:
+            fid_loaders, fid_real = {'test': SyntheticLoader(args.fid, args.num_channels, args.dim_image, 1)}, False
+        else:
+            raise FileNotFoundError(f"dataset files {fdl.paths()} not found. Pass `--opts synthetic True` to run on synthetic images instead.")
+        fid_real = fid_real and find_fid_weights(args.output_root) is not None
+        metric = ComputeMetric(fid_loaders, fm, device, args, results_dir='results' if fid_real else 'results_synthetic')
+        fid = metric.compute_metrics(args.fid)
+        with open(os.path.join(out, "fid.txt"), "w") as f:
+            f.write(f"# FID of {args.fid // 50 * 50} prior samples against {args.fid} test images, {args.fid_dims} Inception features"
+                    f"{'' if fid_real else ' (SYNTHETIC weights or images: not comparable with anything)'}\n{fid}\n")
+        print(f"[prior_report] FID ({args.fid} samples, {args.fid_dims} features): {fid} -> {out}/fid.txt")
     print(f"[prior_report] {args.n_samples} samples -> {out}/samples.png; mean bits/dim {float(bpd.mean()):.4f} over {bpd.numel()} images "
           f"({nfe} evaluations) -> {out}/bits_per_dim.txt")
 
