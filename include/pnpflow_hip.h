@@ -470,6 +470,46 @@ typedef struct pf_likelihood_params {
 int pf_flow_likelihood_rk45(pf_engine* e, const pf_likelihood_params* prm, const float* x_in, const float* eps, float* z_out, double* delta_logp,
                             float* bpd, int64_t* stats, int B, void* stream);
 
+/* ---- sampling the rectified-flow prior (additive: PF_ABI_VERSION unchanged) -----------------------------------------------------------
+ * euler_sampler of image_generation/sampling.py:69-109 (and RectifiedFlow.euler_ode, sde_lib.py:75-94, at sigma_var = 0), quirks kept.  For
+ * i = 0 .. n_steps - 1, N = n_steps:
+ *   num_t = i/N (t_end - t_begin) + t_begin,   dt = 1/N   (NOT the grid spacing (t_end - t_begin)/N: the reference's own step),
+ *   sigma_t = (1 - num_t) sigma_var,   pred = v(x, num_t)   (the net is fed float(num_t) * the solver time scale),
+ *   pred_sigma = pred + sigma_t^2 / (2 noise_scale^2 (1 - num_t)^2) (0.5 num_t (1 - num_t) pred - 0.5 (2 - num_t) x),
+ *   x += pred_sigma dt + sigma_t sqrt(dt) n_i.
+ * One fused kernel per step; the scalars are computed in double on the host and rounded to fp32 once each.  n_i = noise[i] when `noise`
+ * (device [n_steps][B][C][H][W]) is given; otherwise it is drawn inside the kernel from Philox4x32-10/Box-Muller (seed, stream_id) at element
+ * offset i * B*C*H*W: the values pf_fill_normal_at(out, B*C*H*W, seed, stream_id, i * B*C*H*W) writes.  sigma_var == 0: no noise is read or
+ * drawn, the step is x + pred dt.  Nothing synchronises.  x_in, x_out: [B,C,H,W] (may alias).
+ * PF_ERR_INVALID with nothing launched: a NULL engine, prm, x_in or x_out, B <= 0, n_steps < 1, sigma_var < 0, noise_scale <= 0, non-finite
+ * or equal end points, and sigma_var > 0 with a step at num_t = 1. */
+typedef struct pf_rf_sampler_params {
+    double t_begin, t_end;    /* the reference: 1e-3, sde.T = 1 */
+    int32_t n_steps;          /* sde.sample_N */
+    int32_t reserved0;
+    double sigma_var;         /* config.sampling.sigma_variance */
+    double noise_scale;       /* config.sampling.init_noise_scale */
+    uint64_t seed, stream_id; /* Philox key and stream of the in-kernel draw */
+} pf_rf_sampler_params;
+int pf_rf_euler_sampler(pf_engine* e, const pf_rf_sampler_params* prm, const float* x_in, const float* noise, float* x_out, int B, void* stream);
+
+/* dx/dt = v(x, t) from t0 to t1 (either direction) under scipy.integrate.solve_ivp(method='RK45')'s rules (csrc/rk45_control.h), the solve
+ * rk45_sampler (sampling.py:111-153) and RectifiedFlow.ode (sde_lib.py:37-72) make.  The state stays on the device in fp32; time and step in
+ * fp64 on the host; the net is fed float(t) * the solver time scale.  The error norm is the RMS over ALL B*C*H*W entries with scale
+ * atol + rtol max(|y|, |y_new|): SciPy sees the flattened batch as one vector, so the images of a batch share one step sequence (a sample
+ * depends on its batch companions at the level of the tolerance).  Per attempt: six evaluations (FSAL) and one 8-byte read of the norm.
+ *   stats (host int64[3], may be NULL): accepted steps, rejected steps, evaluations (2 + 6 * attempts)
+ * More than max_attempts attempts, a step below 10 ulp of t or a non-finite norm fail with PF_ERR_NUMERIC and no result.  PF_ERR_INVALID with
+ * nothing launched: a NULL engine, prm, x_in or x_out, B <= 0, rtol or atol <= 0, non-finite or equal end points, max_attempts <= 0.
+ * Synchronises `stream`. */
+typedef struct pf_rk45_params {
+    double t0, t1;
+    double rtol, atol;
+    int32_t max_attempts;
+    int32_t reserved0;
+} pf_rk45_params;
+int pf_flow_ode_rk45(pf_engine* e, const pf_rk45_params* prm, const float* x_in, float* x_out, int64_t* stats, int B, void* stream);
+
 /* ---- whole restoration loop --------------------------------------------------------- */
 typedef struct pf_pnp_params {
     int32_t steps;            /* steps_pnp */

@@ -12,6 +12,8 @@ seed-fixed synthetic weights / images (smoke runs without the downloads) and wri
 
 `compute_metrics True` first computes the FID of `fid_samples` (default 5000) prior samples against as many test images
 (pnpflow_amd/compute_metric.py; reference main.py:112-118) at `fid_dims` Inception features (2048, or 64 / 192 / 768), then restores.
+With `model rectified` the samples come from the reference's rectified-flow sampler (pnpflow_amd/image_generation/sampling.py) on the
+config's `sampling` fields; `use_ode_sampler` (rk45 | euler), `sample_N`, `sigma_variance` and `ode_tol` override them.
 
 Multi-GPU: `torchrun --nproc-per-node N main.py --opts ...` - one process per GPU, every
 rank restores its contiguous slice of each test batch, one all_gather of per-image metrics
@@ -101,16 +103,27 @@ class SyntheticLoader:
             yield ((x - lo) / (hi - lo) * 2 - 1).contiguous(), torch.zeros(self.bs)
 
 
+def prior_sampler(args, model, device):
+    """What draws from the prior of `model`: FLOW_MATCHING for the 'ot' / 'indep' U-Net; for 'rectified' the reference's sampler
+    (image_generation/sampling.py) on the RectifiedFlow of the net's config.sampling, with the options `use_ode_sampler` (rk45 | euler),
+    `sample_N`, `sigma_variance` and `ode_tol` overriding its fields."""
+    if args.model != "rectified":
+        from pnpflow_amd.train_flow_matching import FLOW_MATCHING
+        return FLOW_MATCHING(model, device, args)
+    from pnpflow_amd.image_generation.sampling import PriorSampler, rectified_flow_from_config
+    sde = rectified_flow_from_config(model.config, **{k: getattr(args, k, None) for k in ("use_ode_sampler", "sample_N", "sigma_variance", "ode_tol")})
+    return PriorSampler(model, sde, (args.batch_size_ip, args.num_channels, args.dim_image, args.dim_image), device=device)
+
+
 def compute_fid_metric(args, model, model_path, device, world, synthetic):
     """`compute_metrics True` (reference main.py:112-118): FID of `fid_samples` prior samples against one test batch of as many images."""
     from pnpflow_amd.compute_metric import ComputeMetric
     from pnpflow_amd.dataloaders import DataLoaders
     from pnpflow_amd.models import InceptionV3, find_fid_weights
-    from pnpflow_amd.train_flow_matching import FLOW_MATCHING
     if world > 1:
         raise SystemExit("compute_metrics runs on one GPU (the FID's sampling and statistics are not distributed): start it without torchrun")
-    if args.model not in ("ot", "indep"):
-        raise SystemExit(f"compute_metrics samples the flow prior through FLOW_MATCHING, which takes model 'ot' or 'indep', not {args.model!r}")
+    if args.model not in ("ot", "indep", "rectified"):
+        raise SystemExit(f"compute_metrics samples the flow prior of model 'ot' or 'indep' (FLOW_MATCHING) or 'rectified' (image_generation/sampling.py), not {args.model!r}")
     n, dims = int(getattr(args, "fid_samples", 5000)), int(getattr(args, "fid_dims", 2048))
     if dims not in InceptionV3.BLOCK_INDEX_BY_DIM:
         raise SystemExit(f"fid_dims must be one of {sorted(InceptionV3.BLOCK_INDEX_BY_DIM)}, not {dims}")
@@ -125,7 +138,7 @@ def compute_fid_metric(args, model, model_path, device, world, synthetic):
     else:
         raise FileNotFoundError(f"dataset files {dl.paths()} not found. Pass `--opts synthetic True` to run on synthetic images instead.")
     real = not data_synthetic and os.path.isfile(model_path) and find_fid_weights(args.output_root) is not None
-    metric = ComputeMetric(data_loaders, FLOW_MATCHING(model, device, args), device, args, results_dir='results' if real else 'results_synthetic')
+    metric = ComputeMetric(data_loaders, prior_sampler(args, model, device), device, args, results_dir='results' if real else 'results_synthetic')
     fid = metric.compute_metrics(n)
     print(f'Computing metrics done! FID ({n} samples, {dims} features): {fid} -> {metric.save_path}metrics.txt')
 

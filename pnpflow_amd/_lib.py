@@ -70,6 +70,16 @@ class PfLikelihoodParams(C.Structure):
                 ("max_attempts", C.c_int32), ("reserved0", C.c_int32)]
 
 
+class PfRfSamplerParams(C.Structure):
+    _fields_ = [("t_begin", C.c_double), ("t_end", C.c_double), ("n_steps", C.c_int32), ("reserved0", C.c_int32), ("sigma_var", C.c_double),
+                ("noise_scale", C.c_double), ("seed", C.c_uint64), ("stream_id", C.c_uint64)]
+
+
+class PfRk45Params(C.Structure):
+    _fields_ = [("t0", C.c_double), ("t1", C.c_double), ("rtol", C.c_double), ("atol", C.c_double), ("max_attempts", C.c_int32),
+                ("reserved0", C.c_int32)]
+
+
 class PfPnpGsParams(C.Structure):
     _fields_ = [("algo", C.c_int32), ("noise_model", C.c_int32), ("max_iter", C.c_int32), ("first", C.c_int32), ("stop", C.c_int32),
                 ("skip_grad_step", C.c_int32), ("host_sigma_den", C.POINTER(C.c_float)), ("grad_coef", C.c_float), ("use_graph", C.c_int32),
@@ -158,6 +168,8 @@ SIGNATURES = {
     "pf_flow_ode_euler": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pf_flow_likelihood_rk45": (C.c_int, [C.c_void_p, C.POINTER(PfLikelihoodParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
+    "pf_rf_euler_sampler": (C.c_int, [C.c_void_p, C.POINTER(PfRfSamplerParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "pf_flow_ode_rk45": (C.c_int, [C.c_void_p, C.POINTER(PfRk45Params), C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
     "pf_gs_denoiser_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pf_pnp_gs_restore": (C.c_int, [C.c_void_p, C.POINTER(PfDegradation), C.POINTER(PfPnpGsParams), C.c_void_p, C.c_void_p, C.POINTER(C.c_double),
                                     C.POINTER(C.c_double), C.c_int, C.c_void_p, ITER_CB, C.c_void_p]),

@@ -167,7 +167,7 @@ struct pf_engine {
     DFlowState* dflow = nullptr;         // pf_d_flow_forward / pf_d_flow_value_and_grad state (engine_dflow.inc)
     DopriState* dopri = nullptr;         // pf_flow_ode_dopri5 state (engine_dflow.inc)
     PnpGsState* pnpgs = nullptr;         // pf_gs_denoiser_grad / pf_pnp_gs_restore state (engine_pnp_gs.inc)
-    PriorEvalState* prior = nullptr;     // pf_flow_divergence / pf_flow_ode_euler / pf_flow_likelihood_rk45 state (engine_prior_eval.inc)
+    PriorEvalState* prior = nullptr;     // pf_flow_divergence / pf_flow_ode_euler / pf_flow_likelihood_rk45 state (engine_prior_eval.inc), shared by the samplers of engine_rf_sampler.inc
     FlowPriorsState* fprior = nullptr;   // pf_flow_priors_grad / pf_flow_priors_restore state (engine_flow_priors.inc)
     std::vector<CachedGraph*> graphs;    // every live cached graph of the states above (CachedGraph::capture / drop keep the list)
     // profiling
@@ -2208,6 +2208,7 @@ int pf_engine_profile_read(pf_engine* e, int64_t* launches, double* ms_conv_gemm
 #include "engine_dflow.inc"
 #include "engine_pnp_gs.inc"
 #include "engine_prior_eval.inc"
+#include "engine_rf_sampler.inc"
 #include "engine_flow_priors.inc"
 
 // teardown: every solver state goes the way a shape change sends it (graphs dropped, buffers released), then its struct

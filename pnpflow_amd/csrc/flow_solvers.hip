@@ -3,13 +3,15 @@
 //     regulariser (closure, :110-121) and the reverse sweep of T's adjoint;
 //   * the adaptive Dormand-Prince (dopri5) solve of dx/dt = v(x, t) that initialises the latent (inverse_flow_matching, :51-60);
 //   * the prior's evaluation (pnpflow/utils.py:243-270 hut_estimator, pnpflow/image_generation/likelihood.py:116-195): the per-image dot
-//     product eps . (J^T eps) of the Hutchinson estimator, the fp64 log-density entries of the augmented RK45 state and the bits/dim finish.
+//     product eps . (J^T eps) of the Hutchinson estimator, the fp64 log-density entries of the augmented RK45 state and the bits/dim finish;
+//   * the rectified-flow sampler (pnpflow/image_generation/sampling.py:69-109 euler_sampler): one fused Euler / Euler-Maruyama update per step.
 // NCHW fp32 images; every per-image length is a multiple of 4 (float4 lanes: one thread = 4 consecutive values).
 // Reductions are deterministic: per-block fp64 partial sums (a fixed number of blocks per image / tensor, a fixed tree inside the
 // block) then a fixed-order finish - no float atomics, so replays of one input give bit-identical values (LBFGS's strong-Wolfe line
 // search branches on them).
 #include <algorithm>
 #include "pf_common.h"
+#include "philox_normal.h"
 
 namespace pf {
 
@@ -240,6 +242,33 @@ __global__ void bpd_finish_kernel(const double* __restrict__ pz, int nparts, int
     bpd[b] = (float)(-(prior + delta_logp[b]) / (N * 0.6931471805599453) + offset);
 }
 
+
+// ---- rectified-flow sampler: one step of euler_sampler (sampling.py:92-105) -------------------------------------------------------------
+//   pred_sigma = pred + c0 (a1 pred - a2 x),   x <- x + pred_sigma dt + s n
+// every product and sum rounded on its own, in the order torch evaluates the reference's expression (no contraction into an fma).
+// kNoise 0: the deterministic step x + pred dt (c.s == 0: nothing is read or drawn); 1: n read from `noise`; 2: n drawn here - lane q of
+// the tensor takes normals [first + 4q, first + 4q + 4) of the stream (first % 4 == 0: whole Philox counters), the values
+// fill_normal_kernel writes for elem_offset = first.
+template <int kNoise>
+__global__ __launch_bounds__(kThreads) void rf_euler_step4_kernel(float4* __restrict__ x, const float4* __restrict__ pred, const float4* __restrict__ noise,
+                                                                  RfStepCoef c, uint64_t seed, uint64_t stream, uint64_t first, int64_t n4) {
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n4; i += (int64_t)gridDim.x * kThreads) {
+        const float4 a = x[i], p = pred[i];
+        if (kNoise == 0) {
+            x[i] = make_float4(axpy_rn(a.x, c.dt, p.x), axpy_rn(a.y, c.dt, p.y), axpy_rn(a.z, c.dt, p.z), axpy_rn(a.w, c.dt, p.w));
+            continue;
+        }
+        float4 z;
+        if (kNoise == 1) z = noise[i]; else z = normal4((first >> 2) + (uint64_t)i, seed, stream);
+        auto step = [&](float xv, float pv, float zv) {
+            const float inner = __fsub_rn(__fmul_rn(c.a1, pv), __fmul_rn(c.a2, xv));
+            const float ps = __fadd_rn(pv, __fmul_rn(c.c0, inner));
+            return __fadd_rn(axpy_rn(xv, c.dt, ps), __fmul_rn(c.s, zv));
+        };
+        x[i] = make_float4(step(a.x, p.x, z.x), step(a.y, p.y, z.y), step(a.z, p.z, z.z), step(a.w, p.w, z.w));
+    }
+}
+
 }  // namespace
 
 int reduction_parts(int64_t n4) { return (int)std::max<int64_t>(1, std::min<int64_t>((n4 + kThreads - 1) / kThreads, 64)); }
@@ -323,6 +352,19 @@ hipError_t launch_bpd_finish(const float* z, const double* delta_logp, double* p
     const int np = reduction_parts(n / 4);
     hipLaunchKernelGGL(sumsq4_kernel, dim3(np, B), dim3(kThreads), 0, s, (const float4*)z, partial, n / 4);
     hipLaunchKernelGGL(bpd_finish_kernel, dim3((B + 63) / 64), dim3(64), 0, s, (const double*)partial, np, B, (double)n, delta_logp, offset, bpd);
+    return hipGetLastError();
+}
+
+hipError_t launch_rf_euler_step(float* x, const float* pred, const float* noise, const RfStepCoef& c, uint64_t seed, uint64_t stream_id, uint64_t first,
+                                int64_t n, hipStream_t s) {
+    if (n % 4 || first % 4) return hipErrorInvalidValue;
+    const dim3 grid(stream_blocks(n / 4)), block(kThreads);
+    if (c.s == 0.f)
+        hipLaunchKernelGGL(rf_euler_step4_kernel<0>, grid, block, 0, s, (float4*)x, (const float4*)pred, (const float4*)nullptr, c, seed, stream_id, first, n / 4);
+    else if (noise)
+        hipLaunchKernelGGL(rf_euler_step4_kernel<1>, grid, block, 0, s, (float4*)x, (const float4*)pred, (const float4*)noise, c, seed, stream_id, first, n / 4);
+    else
+        hipLaunchKernelGGL(rf_euler_step4_kernel<2>, grid, block, 0, s, (float4*)x, (const float4*)pred, (const float4*)nullptr, c, seed, stream_id, first, n / 4);
     return hipGetLastError();
 }
 

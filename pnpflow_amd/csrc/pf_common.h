@@ -342,6 +342,19 @@ hipError_t launch_rk_aug(const RkAug& c, const double* logp, double* logp_new, d
 // bpd[b] = -(-N/2 ln(2 pi) - 1/2 |z_b|^2 + delta_logp[b]) / (N ln 2) + offset, N = n; partial: >= B * 64 doubles
 hipError_t launch_bpd_finish(const float* z, const double* delta_logp, double* partial, float* bpd, double offset, int B, int64_t n, hipStream_t s);
 
+// rectified-flow sampler (engine_rf_sampler.inc): the scalars of one step of euler_sampler (sampling.py:92-105), computed in double on the
+// host and rounded to fp32 once each, as torch rounds a Python scalar that meets an fp32 tensor
+struct RfStepCoef {
+    float dt;          // fp32(1 / N)
+    float c0;          // fp32(sigma_t^2 / (2 noise_scale^2 (1 - num_t)^2))
+    float a1, a2;      // fp32(0.5 num_t (1 - num_t)), fp32(0.5 (2 - num_t))
+    float s;           // fp32(sigma_t sqrt(dt)); 0: the deterministic step x + pred dt, no noise read or drawn
+};
+// x <- x + (pred + c0 (a1 pred - a2 x)) dt + s n, every operation rounded on its own; n = noise[i] when given, else normal number first + i of the
+// engine's Philox stream (seed, stream_id): what launch_fill_normal writes at elem_offset = first (first % 4 == 0)
+hipError_t launch_rf_euler_step(float* x, const float* pred, const float* noise, const RfStepCoef& c, uint64_t seed, uint64_t stream_id, uint64_t first,
+                                int64_t n, hipStream_t s);
+
 // ---- Prox-PnP with the gradient-step denoiser: glue (prox_pnp.hip) and the Fourier prox (fft2.hip) ---------------------------
 enum { PNPGS_DG = 0, PNPGS_PGD = 1, PNPGS_HQS_MASK = 2, PNPGS_HQS_BLUR = 3, PNPGS_HQS_SR = 4 };      // output form of launch_pnpgs_combine
 constexpr int PNPGS_MAX_PARTS = 256;

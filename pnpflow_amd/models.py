@@ -155,6 +155,42 @@ class _EngineNet:
                                                      stats, B, _lib.current_stream_ptr()), self._h, "pf_flow_likelihood_rk45")
         return z, dlp, bpd, dict(accepted=int(stats[0]), rejected=int(stats[1]), nfev=int(stats[2]))
 
+    # ---- sampling the rectified-flow prior -----------------------------------------------------
+    def rf_euler(self, x: torch.Tensor, n_steps: int, t_begin: float = 1e-3, t_end: float = 1.0, sigma_var: float = 0.0, noise_scale: float = 1.0,
+                 noise: torch.Tensor = None, seed: int = 0, stream_id: int = 0) -> torch.Tensor:
+        """euler_sampler of image_generation/sampling.py:69-109 from the latent `x` (pf_rf_euler_sampler): n_steps evaluations at
+        num_t = i/N (t_end - t_begin) + t_begin with the reference's step dt = 1/N (not the grid spacing), the Euler-Maruyama form when
+        sigma_var > 0.  `noise`: optional (n_steps, B, C, H, W) draws; otherwise the engine's Philox normals (seed, stream_id) are drawn
+        inside the update kernel.  The net sees num_t * the solver time scale.  Nothing synchronises."""
+        x = self._check_images(x, "input")
+        n_steps = int(n_steps)
+        if noise is not None:
+            if tuple(noise.shape) != (n_steps,) + tuple(x.shape):
+                raise ValueError(f"noise of shape {tuple(noise.shape)} does not match (n_steps, B, C, H, W) = {(n_steps,) + tuple(x.shape)}")
+            if not noise.is_cuda:
+                raise _lib.PnpFlowHipError(f"{type(self).__name__} needs GPU tensors (there is no CPU path)")
+            noise = noise.detach().contiguous().float()
+        prm = _lib.PfRfSamplerParams()
+        prm.t_begin, prm.t_end, prm.n_steps, prm.sigma_var, prm.noise_scale = float(t_begin), float(t_end), n_steps, float(sigma_var), float(noise_scale)
+        prm.seed, prm.stream_id = int(seed), int(stream_id)
+        out = torch.empty_like(x)
+        _lib.check(self._lib.pf_rf_euler_sampler(self._h, C.byref(prm), x.data_ptr(), noise.data_ptr() if noise is not None else None, out.data_ptr(),
+                                                 x.shape[0], _lib.current_stream_ptr()), self._h, "pf_rf_euler_sampler")
+        return out
+
+    def ode_rk45(self, x: torch.Tensor, t0: float, t1: float, rtol: float, atol: float, max_attempts: int = 1000):
+        """dx/dt = v(x, t) from t0 to t1 under SciPy's RK45 rules (pf_flow_ode_rk45) -> (x at t1, dict(accepted, rejected, nfev)).
+        The error norm is the RMS over the WHOLE batch, as scipy.integrate.solve_ivp sees the flattened batch: the images of a batch share
+        one step sequence, so a sample depends on its batch companions at the level of the tolerance."""
+        x = self._check_images(x, "input")
+        prm = _lib.PfRk45Params()
+        prm.t0, prm.t1, prm.rtol, prm.atol, prm.max_attempts = float(t0), float(t1), float(rtol), float(atol), int(max_attempts)
+        out = torch.empty_like(x)
+        stats = (C.c_int64 * 3)()
+        _lib.check(self._lib.pf_flow_ode_rk45(self._h, C.byref(prm), x.data_ptr(), out.data_ptr(), stats, x.shape[0], _lib.current_stream_ptr()),
+                   self._h, "pf_flow_ode_rk45")
+        return out, dict(accepted=int(stats[0]), rejected=int(stats[1]), nfev=int(stats[2]))
+
     # ---- debugging: named internal activations of the last forward (NCHW numpy) -----------
     def read_taps(self, B):
         """Internal activations of the last forward as {name: (B,C,H,W) numpy}.  Only

@@ -1,13 +1,15 @@
 """Look at a flow-prior checkpoint: a grid of samples drawn from it and a bits/dim table of images under it.
 
     python tools/prior_report.py --opts dataset celeba model ot [n_samples 16] [integration_method dopri5] [integration_steps 100] [seed 0] [fid N] [fid_dims 2048]
+    python tools/prior_report.py --opts dataset celebahq model rectified [n_samples 16] [use_ode_sampler rk45|euler] [sample_N 100] [sigma_variance 0] [ode_tol 1e-5]
 
 Uses main.py's config surface (config/main_config.yaml, the dataset YAML, then --opts) to build the net and to find the checkpoint
 `<output_root>model/<dataset>/<model>/model_final.pt` and the test images.  Like main.py it FAILS when either is missing, unless
 `--opts synthetic True` opts into seed-fixed synthetic weights / images; the report then goes under `results_synthetic/`.
 
 Writes `<output_root>results[_synthetic]/<dataset>/<model>/prior_report/`:
-    samples.png      n_samples draws (FLOW_MATCHING.generate_samples), postprocessed to [0, 1]
+    samples.png      n_samples draws (FLOW_MATCHING.generate_samples; `model rectified`: the rectified-flow sampler of image_generation/sampling.py
+                     on the config's sampling fields, which the four sampler options override), postprocessed to [0, 1]
     bits_per_dim.txt one row per image: bits/dim, delta_logp, accepted / rejected steps and evaluations of its batch (get_likelihood_fn_rf)
     fid.txt          with `fid N`: the FID of N prior samples against N test images (compute_metric.ComputeMetric at fid_dims features; its own
                      `Epoch: final, FID:` line goes to results[_synthetic]/<dataset>/metrics.txt as main.py's does)
@@ -30,12 +32,14 @@ def parse_args():
     parser.add_argument('--opts', default=None, nargs=argparse.REMAINDER)
     a = parser.parse_args()
     cfg = load_cfg_from_cfg_file(os.path.join(ROOT, 'config', 'main_config.yaml'))
-    extra = dict(n_samples=16, integration_method="dopri5", integration_steps=100, tol=1e-5, n_images=None, fid=0, fid_dims=2048)
+    extra = dict(n_samples=16, integration_method="dopri5", integration_steps=100, tol=1e-5, n_images=None, fid=0, fid_dims=2048,
+                 use_ode_sampler=None, sample_N=None, sigma_variance=None, ode_tol=None)
+    kinds = dict(n_images=int, use_ode_sampler=str, sample_N=int, sigma_variance=float, ode_tol=float)      # of the options whose default is None
     opts = list(a.opts or [])
     for k in list(extra):          # report-only options: taken out of --opts before the config merge (which knows main.py's keys only)
         if k in opts:
             i = opts.index(k)
-            extra[k] = type(extra[k])(opts[i + 1]) if extra[k] is not None else int(opts[i + 1])
+            extra[k] = type(extra[k])(opts[i + 1]) if extra[k] is not None else kinds[k](opts[i + 1])
             del opts[i:i + 2]
     cfg = merge_cfg_from_list(cfg, opts)
     cfg.update(load_cfg_from_cfg_file(os.path.join(ROOT, 'config', 'dataset_config', f'{cfg.dataset}.yaml')))
@@ -51,15 +55,11 @@ def main():
     device = torch.device("cuda", 0)
     if args.seed is not None:
         random.seed(args.seed); torch.manual_seed(args.seed); np.random.seed(args.seed)
-    from main import SyntheticLoader
+    from main import SyntheticLoader, prior_sampler
     from pnpflow_amd import utils
     from pnpflow_amd.dataloaders import DataLoaders
     from pnpflow_amd.image_generation.likelihood import get_likelihood_fn_rf
-    from pnpflow_amd.train_flow_matching import FLOW_MATCHING
 
-    if args.model == "rectified":
-        raise SystemExit("sampling the rectified NCSN++ prior goes through the reference's own sampler (image_generation/sampling.py), "
-                         "which this engine does not implement; the report covers the 'ot' / 'indep' U-Net")
     synthetic = bool(getattr(args, "synthetic", False))
     args.device_index = 0
     (model, state) = utils.define_model(args)
@@ -86,9 +86,12 @@ def main():
     os.makedirs(out, exist_ok=True)
 
     # samples
-    fm = FLOW_MATCHING(model, device, args)
-    imgs = fm.generate_samples(args.integration_method, tol=args.tol, n_samples=args.n_samples, batch_size=args.batch_size_ip,
-                               num_channels=args.num_channels, integration_steps=args.integration_steps)
+    fm = prior_sampler(args, model, device)
+    if args.model == "rectified":
+        imgs = fm.generate_samples(args.n_samples, batch_size=args.batch_size_ip)
+    else:
+        imgs = fm.generate_samples(args.integration_method, tol=args.tol, n_samples=args.n_samples, batch_size=args.batch_size_ip,
+                                   num_channels=args.num_channels, integration_steps=args.integration_steps)
     model.check_numerics()
     grid = utils.postprocess(imgs, args).clamp(0, 1).permute(0, 2, 3, 1).cpu().numpy()          # (B, H, W, C), as save_images hands it over
     utils._imshow_grid(os.path.join(out, "samples.png"), grid, gray=args.num_channels == 1)
